@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X Gaussian-splat hot path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed steps, the arrays the caller of the timed path received in its LAST timed step (images,
+radii, gradients) are written as DIR/<name>.npy, float32 (float64 where computed so), at most 64 MB in all.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (one rank per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE from the environment), or as plain `python bench.py --gpus N`, which starts its own N
@@ -181,9 +185,18 @@ class Scene:
 
     def one_step(self):
         if self.step is not None:
-            self.step(self.camd, self.bg, self.gt_d, self.mask_d, reduce=self.world > 1)
+            self.last = self.step(self.camd, self.bg, self.gt_d, self.mask_d, reduce=self.world > 1)
         else:
-            self.fsession.forward(self.params, self.camd, self.bg, self.deg)
+            self.last = self.fsession.forward(self.params, self.camd, self.bg, self.deg)
+
+    def outputs(self):
+        """What the caller of the last step received: the images and radii it returned, and for fwd+bwd the gradients it left in
+        step.grads."""
+        if self.step is None:
+            return dict(zip(("color", "depth", "alpha", "radii"), self.last))
+        out = dict(zip(("color", "alpha", "radii"), self.last))
+        out.update({f"grad_{k}": v for k, v in self.step.grads.items()})
+        return out
 
     def forward_only(self):
         self.session.forward(self.params, self.camd, self.bg, self.deg)
@@ -239,6 +252,46 @@ def pct(xs):
     a = np.asarray(xs, np.float64)
     return {"median_ms": round(float(np.median(a)), 4), "p10_ms": round(float(np.percentile(a, 10)), 4),
             "p90_ms": round(float(np.percentile(a, 90)), 4)}
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all .npy files of one run together, headers included
+DUMP_WHOLE_BYTES = 1 << 20      # arrays up to this size are always written whole
+
+
+def snapshot_outputs(named):
+    """Device copies of the tensors a caller of the timed path received (name -> tensor; None and non-tensors are dropped), taken
+    right after the timed region so that the untimed work that follows cannot overwrite them."""
+    import torch
+    return {k: v.detach().clone() for k, v in named.items() if isinstance(v, torch.Tensor)}
+
+
+def dump_outputs(path, snap):
+    """--dump-outputs: <path>/<name>.npy for every snapshot tensor, float64 kept, every other dtype as float32.  Over
+    DUMP_LIMIT_BYTES in all, every array larger than DUMP_WHOLE_BYTES keeps the same fraction of its rows (leading dimension of at
+    least 4096, e.g. per-Gaussian arrays) or else of its flattened elements (e.g. images), chosen by a generator seeded with 0: the
+    sample depends on the shapes only, so two builds run with the same arguments write the same elements."""
+    import torch
+    host = {k: (v if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in snap.items()}
+    budget = DUMP_LIMIT_BYTES - 256 * len(host)   # (an .npy header is 128 bytes)
+    big = [k for k, a in host.items() if a.nbytes > DUMP_WHOLE_BYTES]
+    frac = 1.0
+    if sum(a.nbytes for a in host.values()) > budget:
+        small = sum(a.nbytes for k, a in host.items() if k not in big)
+        frac = max(budget - small, 0) / sum(host[k].nbytes for k in big)
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for k, a in host.items():
+        if frac < 1.0 and k in big:
+            if a.ndim < 2 or a.shape[0] < 4096:
+                a = a.reshape(-1)
+            n = a.shape[0]
+            a = a[np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+        written += a.nbytes
+    assert written <= budget, (written, budget)
+    print(f"bench: {len(host)} outputs of the last timed step in {path} ({written / 1e6:.1f} MB"
+          + (f"; {len(big)} large arrays sampled to {frac:.4f} of their rows / elements" if frac < 1.0 else "") + ")",
+          file=sys.stderr, flush=True)
 
 
 def measured_copy_gbs(dev):
@@ -497,8 +550,10 @@ def main_render(a, rank, world, local, dev, rehearsal):
     from mygauhuman_amd.diff_gaussian_rasterization._C import Phase1Loss
     spec = Phase1Loss(*_phase1_targets(wl["W"], wl["H"], dev, seed=rank))   # every view has its own targets
 
+    last = []
+
     def one():
-        step(1, cam, lambda o: o["loss"], fused_loss=spec)
+        last[:] = step(1, cam, lambda o: o["loss"], fused_loss=spec)
 
     def sync():
         if world > 1:
@@ -515,6 +570,11 @@ def main_render(a, rank, world, local, dev, rehearsal):
         step.compact.allgather_ms()
     elapsed, per_step = timed(one, a.steps, sync)
     step.check()
+    if a.dump_outputs and rank == 0:
+        # render()'s output dict and the loss the caller got, and the gradient each leaf holds after the step
+        out_d, loss = last
+        dump_outputs(a.dump_outputs, snapshot_outputs({**out_d, "loss": loss,
+                                                      **{f"grad_{n}": t.grad for n, t in step.leaves.items()}}))
     ex, ar = step.timer.read_ms(), step.ar_timer.read_ms()
     ag = step.compact.allgather_ms() if step.compact is not None else []
     t = torch.tensor([elapsed, float(np.mean(ex)) if ex else 0.0, float(np.mean(ar)) if ar else 0.0, float(np.mean(ag)) if ag else 0.0],
@@ -561,14 +621,19 @@ def self_launch(a, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS) + ["render"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the forward-only / C2 / C5 figures")
     ap.add_argument("--binning", type=int, default=-1, help="0 global radix, 1 tile bucket (default: library default)")
     ap.add_argument("--tune", action="append", default=[], help="key=value tuning knob (gsr_set_tuning), repeatable")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / "
+                         "float64, at most 64 MB in all: a fixed seeded sample of the larger arrays beyond that)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a, sys.argv[1:]))
@@ -638,6 +703,7 @@ def main():
             sc.step.compact.allgather_ms()
     elapsed, per_step = timed(sc.one_step, a.steps, sync)
     clock_after = _lib.clock_probe(1024, 1 << 19, dev)[0]
+    snap = snapshot_outputs(sc.outputs()) if (a.dump_outputs and rank == 0) else None
     ex_ms = sc.step.timer.read_ms() if sc.step is not None else []
     ar_ms = sc.step.ar_timer.read_ms() if sc.step is not None else []
     ag_ms = sc.step.compact.allgather_ms() if (sc.step is not None and sc.step.compact is not None) else []
@@ -767,6 +833,8 @@ def main():
             gt, mask = synthetic.loss_targets(W, H, seed=0)
             out["cpu_baseline"] = cpu_baseline(wl, cameras.make_camera(W, H, 50.0), g, gt, mask, np.zeros(3, np.float32))
         print(json.dumps(out), flush=True)
+        if snap is not None:
+            dump_outputs(a.dump_outputs, snap)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
