@@ -391,6 +391,35 @@ int gsr_lbs_backward(int P, int V, const float *query, const float *normals, con
                      float *dL_dquery, float *dL_dnormals, float *dL_dlbs_offsets, float *dL_dA_pose,
                      float *dL_doff_pose, float *dA_pose_partials, gsr_stream_t stream);
 
+/* Joint-count variants of the four LBS entry points above: the same signatures with a leading J, and [24] becomes [J] in every
+ * shape -- weights[V][J], lbs_offsets[P][J], A_big / A_pose [J][16], bweights[P][J], dL_dlbs_offsets[P][J], dL_dA_pose[J][16],
+ * dA_pose_partials [gsr_lbs_backward_workgroups(P)][J * 12].  Compiled for J = 24 (SMPL; bit-identical to the entry points
+ * without _nj) and J = 55 (SMPL-X); any other J returns GSR_EINVAL before anything runs on the device. */
+int gsr_lbs_forward_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                       const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                       const float *off_big, const float *off_shape, const float *off_pose, const float *R,
+                       const float *Th, int *vert_ids, float *bweights, float *smpl_pts, float *world_pts,
+                       float *transforms, float *translation, float *world_normals, gsr_stream_t stream);
+int gsr_lbs_forward_grid_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                            const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                            const float *off_big, const float *off_shape, const float *off_pose, const float *R,
+                            const float *Th, int *vert_ids, float *bweights, float *smpl_pts, float *world_pts,
+                            float *transforms, float *translation, float *world_normals, char *workspace,
+                            size_t workspace_bytes, int grid_is_built, gsr_stream_t stream);
+int gsr_lbs_forward_cached_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                              const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                              const float *off_big, const float *off_shape, const float *off_pose, const float *R,
+                              const float *Th, int *vert_ids, float *bweights, float *smpl_pts, float *world_pts,
+                              float *transforms, float *translation, float *world_normals, char *workspace,
+                              size_t workspace_bytes, char *nn_cache, size_t nn_cache_bytes, int cache_is_valid,
+                              gsr_stream_t stream);
+int gsr_lbs_backward_nj(int J, int P, int V, const float *query, const float *normals, const int *vert_ids,
+                        const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                        const float *off_big, const float *off_shape, const float *off_pose, const float *R,
+                        const float *dL_dworld_pts, const float *dL_dtransforms, const float *dL_dworld_normals,
+                        float *dL_dquery, float *dL_dnormals, float *dL_dlbs_offsets, float *dL_dA_pose,
+                        float *dL_doff_pose, float *dA_pose_partials, gsr_stream_t stream);
+
 /* Fused SSIM (extension): utils/loss_utils.py:25-66 -- 11x11 Gaussian window (sigma 1.5), zero
  * padding, C1 = 0.01^2, C2 = 0.03^2 -- over `planes` independent H x W planes (batch x channels of the reference's grouped
  * conv2d).  forward: ssim_map[planes][H][W] (may be null) and the three derivative maps dA, dB, dC (all three or none) that
@@ -486,10 +515,20 @@ int gsr_smpl_pose_backward(const float *poses, const float *correct_Rs, const fl
                            const float *dL_dA, const float *dL_drot_mats, float *dL_dposes, float *dL_dcorrect_Rs,
                            float *dL_djoints, gsr_stream_t stream);
 
+/* The same chain for any body model with 2 <= J <= 64 joints (one lane per joint): poses[3J], correct_Rs[J-1][9] or null,
+ * joints[J][3], parents_host[J]; rot_mats[J][9], A[J][16]; dL_dA[J][16], dL_drot_mats[J][9] -> dL_dposes[3J],
+ * dL_dcorrect_Rs[J-1][9], dL_djoints[J][3].  J = 24 is gsr_smpl_pose_forward / _backward bit for bit; SMPL-X is J = 55.
+ * Any other J returns GSR_EINVAL before anything runs on the device. */
+int gsr_body_pose_forward(int J, const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
+                          float *rot_mats, float *A, gsr_stream_t stream);
+int gsr_body_pose_backward(int J, const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
+                           const float *dL_dA, const float *dL_drot_mats, float *dL_dposes, float *dL_dcorrect_Rs,
+                           float *dL_djoints, gsr_stream_t stream);
+
 /* Row-major matrix-vector products for the SMPL pose blend shapes (scene/gaussian_model.py:805-811,827-839):
  *   gsr_gemv_rows:   out[r] = sum_k mat[r][k] * vec[k]          (offsets[V*3] = posedirs[V*3][207] . pose_feature[207])
  *   gsr_gemv_rows_t: dvec[k] = sum_r dout[r] * mat[r][k]        (its backward w.r.t. the pose feature; dvec is overwritten)
- * cols <= 256. */
+ * cols <= 512 (SMPL-X: posedirs[10475*3][486]); up to 256 columns run the 4-columns-per-lane kernel, above it 8 per lane. */
 int gsr_gemv_rows(int rows, int cols, const float *mat, const float *vec, float *out, gsr_stream_t stream);
 int gsr_gemv_rows_t(int rows, int cols, const float *mat, const float *dout, float *dvec, gsr_stream_t stream);
 

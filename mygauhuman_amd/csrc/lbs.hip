@@ -21,7 +21,8 @@
 
 namespace gsr {
 
-constexpr int NJ = 24;
+// joint counts with a compiled instantiation of the per-point kernels: 24 (SMPL), 55 (SMPL-X: 22 body + jaw + 2 eyes + 2 x 15 hand)
+constexpr int NJ_SMPL = 24, NJ_SMPLX = 55;
 constexpr int LBS_BLOCK = 256;
 constexpr int VTILE = 1024;
 
@@ -372,6 +373,7 @@ __device__ __forceinline__ void mat3_mul(const float *A, const float *B, float *
 }
 
 // blend weights of one point (scene/gaussian_model.py:776-781)
+template <int NJ>
 __device__ __forceinline__ void blend_weights(const float *w_row, const float *off_row, float *bw) {
 #pragma unroll
   for (int j = 0; j < NJ; j++) bw[j] = w_row[j];
@@ -394,6 +396,7 @@ __device__ __forceinline__ void blend_weights(const float *w_row, const float *o
 }
 
 // rows 0..2 of the blended 4x4 transform: out[12] = sum_j bw[j] * A[j][0..11]   (A in LDS)
+template <int NJ>
 __device__ __forceinline__ void blend_A(const float *bw, const float *sA, float *out) {
 #pragma unroll
   for (int k = 0; k < 12; k++) out[k] = 0.f;
@@ -419,7 +422,47 @@ __device__ __forceinline__ void blend_A(const float *bw, const float *sA, float 
   }
 }
 
-template <bool GRID>
+// ---- NJ = 55 (SMPL-X): the weights are streamed, not held.  bw[55] (and g_bw[55] in the backward) under the loops' dynamic joint
+// index went to scratch (224 / 448 B per lane); fully unrolled, the loops' LDS operands were hoisted and the kernels reached 256 VGPRs
+// + 256 AGPRs + 4 KB of scratch.  Instead one pass over the point's row gathers the softmax statistics (max, sum) and every later
+// loop regenerates bw[j] from its row entry -- the same expression as blend_weights, so the same bits -- at the cost of a
+// logf / expf per joint and pass; the rows stay in L1 / L2 between the passes.
+struct StreamedWeights {
+  const float *w, *off;  // the point's rows: weights[vertex][NJ], lbs_offsets[p][NJ] (null: no offsets, bw = w)
+  float mx, sum;
+  __device__ __forceinline__ float z(int j) const { return logf(w[j] + 1e-9f) + off[j]; }
+  __device__ __forceinline__ float operator[](int j) const { return off ? expf(z(j) - mx) / sum : w[j]; }
+};
+template <int NJ>
+__device__ __forceinline__ StreamedWeights streamed_weights(const float *w_row, const float *off_row) {
+  StreamedWeights b = {w_row, off_row, 0.f, 1.f};
+  if (off_row) {
+    float mx = -INFINITY;
+    for (int j = 0; j < NJ; j++) mx = fmaxf(mx, b.z(j));
+    float sum = 0.f;
+    for (int j = 0; j < NJ; j++) sum += expf(b.z(j) - mx);
+    b.mx = mx, b.sum = sum;
+  }
+  return b;
+}
+// both blends in one pass over the joints (and the optional bweights row store)
+template <int NJ>
+__device__ __forceinline__ void blend_A2_streamed(const StreamedWeights &bw, const float *sAb, const float *sAp, float *Ab, float *Ap,
+                                                  float *bw_out) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) Ab[k] = Ap[k] = 0.f;
+  for (int j = 0; j < NJ; j++) {
+    const float b = bw[j];
+    if (bw_out) bw_out[j] = b;
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+      Ab[k] += b * sAb[16 * j + k];
+      Ap[k] += b * sAp[16 * j + k];
+    }
+  }
+}
+
+template <int NJ, bool GRID>
 __global__ __launch_bounds__(LBS_BLOCK) void lbs_forward_kernel(const LbsArgs a) {
   __shared__ float svx[GRID ? 1 : VTILE], svy[GRID ? 1 : VTILE], svz[GRID ? 1 : VTILE];
   __shared__ __attribute__((aligned(16))) float sAb[NJ * 16], sAp[NJ * 16];
@@ -479,14 +522,20 @@ __global__ __launch_bounds__(LBS_BLOCK) void lbs_forward_kernel(const LbsArgs a)
   }
   if (!live) return;
   if (a.vert_ids) a.vert_ids[p] = bid;
-  float bw[NJ];
-  blend_weights(a.weights + (size_t)bid * NJ, a.lbs_offsets ? a.lbs_offsets + (size_t)p * NJ : nullptr, bw);
-  if (a.bweights)
-#pragma unroll
-    for (int j = 0; j < NJ; j++) a.bweights[(size_t)p * NJ + j] = bw[j];
   float Ab[12], Ap[12];
-  blend_A(bw, sAb, Ab);
-  blend_A(bw, sAp, Ap);
+  if constexpr (NJ == NJ_SMPL) {
+    float bw[NJ];
+    blend_weights<NJ>(a.weights + (size_t)bid * NJ, a.lbs_offsets ? a.lbs_offsets + (size_t)p * NJ : nullptr, bw);
+    if (a.bweights)
+#pragma unroll
+      for (int j = 0; j < NJ; j++) a.bweights[(size_t)p * NJ + j] = bw[j];
+    blend_A<NJ>(bw, sAb, Ab);
+    blend_A<NJ>(bw, sAp, Ap);
+  } else {
+    const StreamedWeights bw =
+        streamed_weights<NJ>(a.weights + (size_t)bid * NJ, a.lbs_offsets ? a.lbs_offsets + (size_t)p * NJ : nullptr);
+    blend_A2_streamed<NJ>(bw, sAb, sAp, Ab, Ap, a.bweights ? a.bweights + (size_t)p * NJ : nullptr);
+  }
   const float Rb[9] = {Ab[0], Ab[1], Ab[2], Ab[4], Ab[5], Ab[6], Ab[8], Ab[9], Ab[10]};
   float Ri[9];
   inv3(Rb, Ri);
@@ -542,15 +591,17 @@ struct LbsBwdArgs {
   const int *vert_ids;
   const float *dL_dworld_pts, *dL_dtransforms, *dL_dworld_normals;
   float *dL_dquery, *dL_dnormals, *dL_dlbs_offsets, *dL_dA_pose, *dL_doff_pose;
-  float *partials;  // [workgroups][24 * 12] per-workgroup dA_pose sums (no atomics) or null
+  float *partials;  // [workgroups][NJ * 12] per-workgroup dA_pose sums (no atomics) or null
 };
 
-// (amdgpu_waves_per_eu(4): the allocator stopped at 132 VGPRs = three waves per SIMD where the 40 KB of LDS admit four; at 128 with
-// four spilled registers the kernel takes 25.6 instead of 32.9 us in the render() frame.  The same hint on the forward kernel -- 108
-// VGPRs, asked for 80 -- spills in the search loop: 76 instead of 54 us.)
-__global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) void lbs_backward_kernel(const LbsBwdArgs a) {
+// (amdgpu_waves_per_eu(4) at NJ = 24: the allocator stopped at 132 VGPRs = three waves per SIMD where the 40 KB of LDS admit four; at
+// 128 with four spilled registers the kernel takes 25.6 instead of 32.9 us in the render() frame.  The same hint on the forward kernel
+// -- 108 VGPRs, asked for 80 -- spills in the search loop: 76 instead of 54 us.  At NJ = 55 the 75 KB of LDS admit two workgroups
+// per CU, i.e. two waves per SIMD: the hint is 2, which leaves the allocator 256 VGPRs for bw[55] and g_bw[55] without scratch.)
+template <int NJ>
+__global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(NJ == NJ_SMPL ? 4 : 2))) void lbs_backward_kernel(const LbsBwdArgs a) {
   __shared__ __attribute__((aligned(16))) float sAb[NJ * 16], sAp[NJ * 16];
-  constexpr int ROW = NJ + 12 + 1;                // bw[24] | g_Ap[12] | pad (odd stride: conflict-free column reads)
+  constexpr int ROW = (NJ + 12) | 1;              // bw[NJ] | g_Ap[12] | pad to an odd stride (conflict-free row writes, column reads)
   __shared__ float s_rows[LBS_BLOCK * ROW];       // per-point operands of the workgroup-level dA_pose product
   for (int k = threadIdx.x; k < NJ * 16; k += LBS_BLOCK) {
     sAb[k] = a.A_big[k];
@@ -561,11 +612,18 @@ __global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
   const int p = blockIdx.x * LBS_BLOCK + threadIdx.x;
   if (p < a.P) {
     const int bid = a.vert_ids[p];
-    float bw[NJ];
-    blend_weights(a.weights + (size_t)bid * NJ, a.lbs_offsets ? a.lbs_offsets + (size_t)p * NJ : nullptr, bw);
+    const float *w_row = a.weights + (size_t)bid * NJ, *off_row = a.lbs_offsets ? a.lbs_offsets + (size_t)p * NJ : nullptr;
     float Ab[12], Ap[12];
-    blend_A(bw, sAb, Ab);
-    blend_A(bw, sAp, Ap);
+    [[maybe_unused]] float bw[NJ == NJ_SMPL ? NJ : 1];
+    [[maybe_unused]] StreamedWeights sbw;
+    if constexpr (NJ == NJ_SMPL) {
+      blend_weights<NJ>(w_row, off_row, bw);
+      blend_A<NJ>(bw, sAb, Ab);
+      blend_A<NJ>(bw, sAp, Ap);
+    } else {
+      sbw = streamed_weights<NJ>(w_row, off_row);
+      blend_A2_streamed<NJ>(sbw, sAb, sAp, Ab, Ap, nullptr);
+    }
     const float Rb[9] = {Ab[0], Ab[1], Ab[2], Ab[4], Ab[5], Ab[6], Ab[8], Ab[9], Ab[10]};
     float Ri[9];
     inv3(Rb, Ri);
@@ -661,6 +719,27 @@ __global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     const float g_Ab[12] = {g_Rb[0], g_Rb[1], g_Rb[2], g_tb[0], g_Rb[3], g_Rb[4], g_Rb[5], g_tb[1], g_Rb[6], g_Rb[7], g_Rb[8], g_tb[2]};
     const float g_Ap[12] = {g_Rp[0], g_Rp[1], g_Rp[2], g_tp[0], g_Rp[3], g_Rp[4], g_Rp[5], g_tp[1], g_Rp[6], g_Rp[7], g_Rp[8], g_tp[2]};
     // dA_pose[j][k] += bw[j] g_Ap[k]  (workgroup-level LDS accumulation) ; g_bw[j] = <g_Ab, A_big[j]> + <g_Ap, A_pose[j]>
+    if constexpr (NJ != NJ_SMPL) {  // streamed: g_bw[j] is regenerated like bw[j] (24 LDS reads + FMAs per joint and pass)
+      auto g_bw_at = [&](int j) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; k++) s += g_Ab[k] * sAb[16 * j + k] + g_Ap[k] * sAp[16 * j + k];
+        return s;
+      };
+      const bool dA = a.dL_dA_pose, doff = a.dL_dlbs_offsets && a.lbs_offsets;
+      float dot = 0.f;
+      if (dA || doff)
+        for (int j = 0; j < NJ; j++) {
+          const float b = sbw[j];
+          if (dA) s_rows[threadIdx.x * ROW + j] = b;
+          if (doff) dot += b * g_bw_at(j);
+        }
+      if (dA)
+#pragma unroll
+        for (int k = 0; k < 12; k++) s_rows[threadIdx.x * ROW + NJ + k] = g_Ap[k];
+      if (doff)  // softmax backward: g_z[j] = bw[j] (g_bw[j] - sum_i bw[i] g_bw[i])
+        for (int j = 0; j < NJ; j++) a.dL_dlbs_offsets[(size_t)p * NJ + j] = sbw[j] * (g_bw_at(j) - dot);
+    } else {
     float g_bw[NJ];
 #pragma unroll 2
     for (int j = 0; j < NJ; j++) {
@@ -682,9 +761,10 @@ __global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
 #pragma unroll
       for (int j = 0; j < NJ; j++) a.dL_dlbs_offsets[(size_t)p * NJ + j] = bw[j] * (g_bw[j] - dot);
     }
+    }
   }
   __syncthreads();
-  // dA_pose[j][k] = sum over the workgroup's points of bw[p][j] * g_Ap[p][k]: a [24 x 256] x [256 x 12] product out of LDS,
+  // dA_pose[j][k] = sum over the workgroup's points of bw[p][j] * g_Ap[p][k]: a [NJ x 256] x [256 x 12] product out of LDS,
   // one output entry per thread, then one atomic per entry and workgroup
   if (a.dL_dA_pose)
     for (int e = threadIdx.x; e < NJ * 12; e += LBS_BLOCK) {
@@ -698,6 +778,134 @@ __global__ __launch_bounds__(LBS_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) 
     }
 }
 
+// ---- host side: one implementation per entry point, the joint count a runtime argument dispatched to the compiled instantiations
+static bool lbs_joints_ok(const char *who, int J) {
+  if (J == NJ_SMPL || J == NJ_SMPLX) return true;
+  set_error("%s: J = %d joints is not supported (compiled joint counts: %d for SMPL, %d for SMPL-X)", who, J, NJ_SMPL, NJ_SMPLX);
+  return false;
+}
+
+template <bool GRID>
+static void launch_lbs_forward(int J, dim3 grid, dim3 block, hipStream_t stream, const LbsArgs &a) {
+  if (J == NJ_SMPLX)
+    hipLaunchKernelGGL((lbs_forward_kernel<NJ_SMPLX, GRID>), grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL((lbs_forward_kernel<NJ_SMPL, GRID>), grid, block, 0, stream, a);
+}
+
+static int lbs_forward_args_ok(const char *who, int J, int P, int V, const float *query, const float *smpl_verts, const float *weights,
+                               const float *A_big, const float *A_pose, const float *off_big, const float *off_shape,
+                               const float *off_pose, const float *R, const float *Th, const float *world_pts) {
+  if (!lbs_joints_ok(who, J)) return GSR_EINVAL;
+  if (P < 0 || V <= 0 || (P > 0 && (!query || !smpl_verts || !weights || !A_big || !A_pose || !off_big || !off_shape ||
+                                    !off_pose || !R || !Th || !world_pts))) {
+    set_error("%s: bad arguments", who);
+    return GSR_EINVAL;
+  }
+  return GSR_OK;
+}
+
+static int lbs_forward(const char *who, int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                       const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
+                       const float *off_shape, const float *off_pose, const float *R, const float *Th, int *vert_ids, float *bweights,
+                       float *smpl_pts, float *world_pts, float *transforms, float *translation, float *world_normals,
+                       gsr_stream_t stream_) {
+  int rc = lbs_forward_args_ok(who, J, P, V, query, smpl_verts, weights, A_big, A_pose, off_big, off_shape, off_pose, R, Th, world_pts);
+  if (rc != GSR_OK) return rc;
+  if (P == 0) return GSR_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
+               vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, nullptr};
+  launch_lbs_forward<false>(J, dim3((P + LBS_BLOCK - 1) / LBS_BLOCK), dim3(LBS_BLOCK), stream, a);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+static int lbs_forward_grid(const char *who, int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                            const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                            const float *off_big, const float *off_shape, const float *off_pose, const float *R, const float *Th,
+                            int *vert_ids, float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
+                            float *world_normals, char *workspace, size_t workspace_bytes, int grid_is_built, gsr_stream_t stream_) {
+  int rc = lbs_forward_args_ok(who, J, P, V, query, smpl_verts, weights, A_big, A_pose, off_big, off_shape, off_pose, R, Th, world_pts);
+  if (rc != GSR_OK) return rc;
+  if (P == 0) return GSR_OK;
+  if (!workspace || workspace_bytes < grid_workspace_bytes(V) || reinterpret_cast<size_t>(workspace) % 16 != 0) {
+    set_error("%s: workspace of %zu bytes (16-byte aligned) required, got %zu", who, grid_workspace_bytes(V), workspace_bytes);
+    return GSR_EINVAL;
+  }
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (!grid_is_built) hipLaunchKernelGGL(lbs_grid_build_kernel, dim3(1), dim3(GRID_BLOCK), 0, stream, V, smpl_verts, workspace);
+  LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
+               vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, workspace, nullptr, nullptr,
+               nullptr, nullptr};
+  launch_lbs_forward<true>(J, dim3((P + LBS_BLOCK - 1) / LBS_BLOCK), dim3(LBS_BLOCK), stream, a);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+static int lbs_forward_cached(const char *who, int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                              const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                              const float *off_big, const float *off_shape, const float *off_pose, const float *R, const float *Th,
+                              int *vert_ids, float *bweights, float *smpl_pts, float *world_pts, float *transforms,
+                              float *translation, float *world_normals, char *workspace, size_t workspace_bytes, char *nn_cache,
+                              size_t nn_cache_bytes_, int cache_is_valid, gsr_stream_t stream_) {
+  int rc = lbs_forward_args_ok(who, J, P, V, query, smpl_verts, weights, A_big, A_pose, off_big, off_shape, off_pose, R, Th, world_pts);
+  if (rc != GSR_OK) return rc;
+  if (P == 0) return GSR_OK;
+  if (!workspace || workspace_bytes < grid_workspace_bytes(V) || reinterpret_cast<size_t>(workspace) % 16 != 0) {
+    set_error("%s: grid workspace of %zu bytes (16-byte aligned, built by gsr_lbs_grid_build) required, got %zu", who,
+              grid_workspace_bytes(V), workspace_bytes);
+    return GSR_EINVAL;
+  }
+  if (!nn_cache || nn_cache_bytes_ < nn_cache_bytes((size_t)P) || reinterpret_cast<size_t>(nn_cache) % 16 != 0) {
+    set_error("%s: cache buffer of %zu bytes (16-byte aligned) required, got %zu", who, nn_cache_bytes((size_t)P), nn_cache_bytes_);
+    return GSR_EINVAL;
+  }
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  NnCacheView c = nn_cache_view(nn_cache, (size_t)P);
+  LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
+               vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, workspace, nullptr, nullptr,
+               nullptr, nullptr};
+  const dim3 grid((P + LBS_BLOCK - 1) / LBS_BLOCK), block(LBS_BLOCK);
+  if (!cache_is_valid) {  // full search; the entries are made on the way
+    GSR_HIP(zero_async(c.count, 64, stream));
+    a.cache_entry = c.entry, a.cache_ids = c.ids;
+    launch_lbs_forward<true>(J, grid, block, stream, a);
+  } else {
+    hipLaunchKernelGGL(nn_cache_update_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, query, workspace, c);
+    a.given_ids = c.ids, a.cache_count = c.count;
+    launch_lbs_forward<true>(J, grid, block, stream, a);
+  }
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+static int lbs_backward(const char *who, int J, int P, int V, const float *query, const float *normals, const int *vert_ids,
+                        const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
+                        const float *off_shape, const float *off_pose, const float *R, const float *dL_dworld_pts,
+                        const float *dL_dtransforms, const float *dL_dworld_normals, float *dL_dquery, float *dL_dnormals,
+                        float *dL_dlbs_offsets, float *dL_dA_pose, float *dL_doff_pose, float *dA_pose_partials,
+                        gsr_stream_t stream_) {
+  if (!lbs_joints_ok(who, J)) return GSR_EINVAL;
+  if (P < 0 || V <= 0 || (P > 0 && (!query || !vert_ids || !weights || !A_big || !A_pose || !off_big || !off_shape ||
+                                    !off_pose || !R || !dL_dquery))) {
+    set_error("%s: bad arguments", who);
+    return GSR_EINVAL;
+  }
+  if (P == 0) return GSR_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  LbsBwdArgs a = {P, V, query, normals, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, vert_ids,
+                  dL_dworld_pts, dL_dtransforms, dL_dworld_normals, dL_dquery, dL_dnormals, dL_dlbs_offsets, dL_dA_pose,
+                  dL_doff_pose, dL_dA_pose ? dA_pose_partials : nullptr};
+  const dim3 grid((P + LBS_BLOCK - 1) / LBS_BLOCK), block(LBS_BLOCK);
+  if (J == NJ_SMPLX)
+    hipLaunchKernelGGL(lbs_backward_kernel<NJ_SMPLX>, grid, block, 0, stream, a);
+  else
+    hipLaunchKernelGGL(lbs_backward_kernel<NJ_SMPL>, grid, block, 0, stream, a);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
 }  // namespace gsr
 
 extern "C" {
@@ -706,20 +914,20 @@ int gsr_lbs_forward(int P, int V, const float *query, const float *normals, cons
                     const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
                     const float *off_shape, const float *off_pose, const float *R, const float *Th, int *vert_ids,
                     float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
-                    float *world_normals, gsr_stream_t stream_) {
-  if (P < 0 || V <= 0 || (P > 0 && (!query || !smpl_verts || !weights || !A_big || !A_pose || !off_big || !off_shape ||
-                                    !off_pose || !R || !Th || !world_pts))) {
-    gsr::set_error("gsr_lbs_forward: bad arguments");
-    return GSR_EINVAL;
-  }
-  if (P == 0) return GSR_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  gsr::LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
-                    vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, nullptr};
-  hipLaunchKernelGGL(gsr::lbs_forward_kernel<false>, dim3((P + gsr::LBS_BLOCK - 1) / gsr::LBS_BLOCK), dim3(gsr::LBS_BLOCK), 0,
-                     stream, a);
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                    float *world_normals, gsr_stream_t stream) {
+  return gsr::lbs_forward("gsr_lbs_forward", gsr::NJ_SMPL, P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose,
+                          off_big, off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts, transforms, translation,
+                          world_normals, stream);
+}
+
+int gsr_lbs_forward_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts, const float *weights,
+                       const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
+                       const float *off_shape, const float *off_pose, const float *R, const float *Th, int *vert_ids,
+                       float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
+                       float *world_normals, gsr_stream_t stream) {
+  return gsr::lbs_forward("gsr_lbs_forward_nj", J, P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big,
+                          off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts, transforms, translation,
+                          world_normals, stream);
 }
 
 int gsr_lbs_backward_workgroups(int P) { return P > 0 ? (P + gsr::LBS_BLOCK - 1) / gsr::LBS_BLOCK : 0; }
@@ -761,28 +969,20 @@ int gsr_lbs_forward_grid(int P, int V, const float *query, const float *normals,
                          const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
                          const float *off_shape, const float *off_pose, const float *R, const float *Th, int *vert_ids,
                          float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
-                         float *world_normals, char *workspace, size_t workspace_bytes, int grid_is_built, gsr_stream_t stream_) {
-  if (P < 0 || V <= 0 || (P > 0 && (!query || !smpl_verts || !weights || !A_big || !A_pose || !off_big || !off_shape ||
-                                    !off_pose || !R || !Th || !world_pts))) {
-    gsr::set_error("gsr_lbs_forward_grid: bad arguments");
-    return GSR_EINVAL;
-  }
-  if (P == 0) return GSR_OK;
-  if (!workspace || workspace_bytes < gsr::grid_workspace_bytes(V) || reinterpret_cast<size_t>(workspace) % 16 != 0) {
-    gsr::set_error("gsr_lbs_forward_grid: workspace of %zu bytes (16-byte aligned) required, got %zu",
-                   gsr::grid_workspace_bytes(V), workspace_bytes);
-    return GSR_EINVAL;
-  }
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (!grid_is_built)
-    hipLaunchKernelGGL(gsr::lbs_grid_build_kernel, dim3(1), dim3(gsr::GRID_BLOCK), 0, stream, V, smpl_verts, workspace);
-  gsr::LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
-                    vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, workspace, nullptr, nullptr,
-                    nullptr, nullptr};
-  hipLaunchKernelGGL(gsr::lbs_forward_kernel<true>, dim3((P + gsr::LBS_BLOCK - 1) / gsr::LBS_BLOCK), dim3(gsr::LBS_BLOCK), 0,
-                     stream, a);
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                         float *world_normals, char *workspace, size_t workspace_bytes, int grid_is_built, gsr_stream_t stream) {
+  return gsr::lbs_forward_grid("gsr_lbs_forward_grid", gsr::NJ_SMPL, P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big,
+                               A_pose, off_big, off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts, transforms,
+                               translation, world_normals, workspace, workspace_bytes, grid_is_built, stream);
+}
+
+int gsr_lbs_forward_grid_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                            const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                            const float *off_big, const float *off_shape, const float *off_pose, const float *R, const float *Th,
+                            int *vert_ids, float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
+                            float *world_normals, char *workspace, size_t workspace_bytes, int grid_is_built, gsr_stream_t stream) {
+  return gsr::lbs_forward_grid("gsr_lbs_forward_grid_nj", J, P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose,
+                               off_big, off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts, transforms, translation,
+                               world_normals, workspace, workspace_bytes, grid_is_built, stream);
 }
 
 size_t gsr_lbs_nn_cache_bytes(int P) { return gsr::nn_cache_bytes(P > 0 ? (size_t)P : 1); }
@@ -792,40 +992,23 @@ int gsr_lbs_forward_cached(int P, int V, const float *query, const float *normal
                            const float *off_shape, const float *off_pose, const float *R, const float *Th, int *vert_ids,
                            float *bweights, float *smpl_pts, float *world_pts, float *transforms, float *translation,
                            float *world_normals, char *workspace, size_t workspace_bytes, char *nn_cache, size_t nn_cache_bytes,
-                           int cache_is_valid, gsr_stream_t stream_) {
-  if (P < 0 || V <= 0 || (P > 0 && (!query || !smpl_verts || !weights || !A_big || !A_pose || !off_big || !off_shape ||
-                                    !off_pose || !R || !Th || !world_pts))) {
-    gsr::set_error("gsr_lbs_forward_cached: bad arguments");
-    return GSR_EINVAL;
-  }
-  if (P == 0) return GSR_OK;
-  if (!workspace || workspace_bytes < gsr::grid_workspace_bytes(V) || reinterpret_cast<size_t>(workspace) % 16 != 0) {
-    gsr::set_error("gsr_lbs_forward_cached: grid workspace of %zu bytes (16-byte aligned, built by gsr_lbs_grid_build) required, got %zu",
-                   gsr::grid_workspace_bytes(V), workspace_bytes);
-    return GSR_EINVAL;
-  }
-  if (!nn_cache || nn_cache_bytes < gsr::nn_cache_bytes((size_t)P) || reinterpret_cast<size_t>(nn_cache) % 16 != 0) {
-    gsr::set_error("gsr_lbs_forward_cached: cache buffer of %zu bytes (16-byte aligned) required, got %zu", gsr::nn_cache_bytes((size_t)P),
-                   nn_cache_bytes);
-    return GSR_EINVAL;
-  }
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  gsr::NnCacheView c = gsr::nn_cache_view(nn_cache, (size_t)P);
-  gsr::LbsArgs a = {P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, Th,
-                    vert_ids, bweights, smpl_pts, world_pts, transforms, translation, world_normals, workspace, nullptr, nullptr,
-                    nullptr, nullptr};
-  const dim3 grid((P + gsr::LBS_BLOCK - 1) / gsr::LBS_BLOCK), block(gsr::LBS_BLOCK);
-  if (!cache_is_valid) {  // full search; the entries are made on the way
-    GSR_HIP(gsr::zero_async(c.count, 64, stream));
-    a.cache_entry = c.entry, a.cache_ids = c.ids;
-    hipLaunchKernelGGL(gsr::lbs_forward_kernel<true>, grid, block, 0, stream, a);
-  } else {
-    hipLaunchKernelGGL(gsr::nn_cache_update_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, query, workspace, c);
-    a.given_ids = c.ids, a.cache_count = c.count;
-    hipLaunchKernelGGL(gsr::lbs_forward_kernel<true>, grid, block, 0, stream, a);
-  }
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                           int cache_is_valid, gsr_stream_t stream) {
+  return gsr::lbs_forward_cached("gsr_lbs_forward_cached", gsr::NJ_SMPL, P, V, query, normals, smpl_verts, weights, lbs_offsets,
+                                 A_big, A_pose, off_big, off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts,
+                                 transforms, translation, world_normals, workspace, workspace_bytes, nn_cache, nn_cache_bytes,
+                                 cache_is_valid, stream);
+}
+
+int gsr_lbs_forward_cached_nj(int J, int P, int V, const float *query, const float *normals, const float *smpl_verts,
+                              const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
+                              const float *off_big, const float *off_shape, const float *off_pose, const float *R, const float *Th,
+                              int *vert_ids, float *bweights, float *smpl_pts, float *world_pts, float *transforms,
+                              float *translation, float *world_normals, char *workspace, size_t workspace_bytes, char *nn_cache,
+                              size_t nn_cache_bytes, int cache_is_valid, gsr_stream_t stream) {
+  return gsr::lbs_forward_cached("gsr_lbs_forward_cached_nj", J, P, V, query, normals, smpl_verts, weights, lbs_offsets, A_big,
+                                 A_pose, off_big, off_shape, off_pose, R, Th, vert_ids, bweights, smpl_pts, world_pts, transforms,
+                                 translation, world_normals, workspace, workspace_bytes, nn_cache, nn_cache_bytes, cache_is_valid,
+                                 stream);
 }
 
 int gsr_lbs_backward(int P, int V, const float *query, const float *normals, const int *vert_ids, const float *weights,
@@ -833,19 +1016,20 @@ int gsr_lbs_backward(int P, int V, const float *query, const float *normals, con
                      const float *off_shape, const float *off_pose, const float *R, const float *dL_dworld_pts,
                      const float *dL_dtransforms, const float *dL_dworld_normals, float *dL_dquery, float *dL_dnormals,
                      float *dL_dlbs_offsets, float *dL_dA_pose, float *dL_doff_pose, float *dA_pose_partials,
-                     gsr_stream_t stream_) {
-  if (P < 0 || V <= 0 || (P > 0 && (!query || !vert_ids || !weights || !A_big || !A_pose || !off_big || !off_shape ||
-                                    !off_pose || !R || !dL_dquery))) {
-    gsr::set_error("gsr_lbs_backward: bad arguments");
-    return GSR_EINVAL;
-  }
-  if (P == 0) return GSR_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  gsr::LbsBwdArgs a = {P, V, query, normals, weights, lbs_offsets, A_big, A_pose, off_big, off_shape, off_pose, R, vert_ids,
-                       dL_dworld_pts, dL_dtransforms, dL_dworld_normals, dL_dquery, dL_dnormals, dL_dlbs_offsets, dL_dA_pose,
-                       dL_doff_pose, dL_dA_pose ? dA_pose_partials : nullptr};
-  hipLaunchKernelGGL(gsr::lbs_backward_kernel, dim3((P + gsr::LBS_BLOCK - 1) / gsr::LBS_BLOCK), dim3(gsr::LBS_BLOCK), 0, stream, a);
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                     gsr_stream_t stream) {
+  return gsr::lbs_backward("gsr_lbs_backward", gsr::NJ_SMPL, P, V, query, normals, vert_ids, weights, lbs_offsets, A_big, A_pose,
+                           off_big, off_shape, off_pose, R, dL_dworld_pts, dL_dtransforms, dL_dworld_normals, dL_dquery,
+                           dL_dnormals, dL_dlbs_offsets, dL_dA_pose, dL_doff_pose, dA_pose_partials, stream);
+}
+
+int gsr_lbs_backward_nj(int J, int P, int V, const float *query, const float *normals, const int *vert_ids, const float *weights,
+                        const float *lbs_offsets, const float *A_big, const float *A_pose, const float *off_big,
+                        const float *off_shape, const float *off_pose, const float *R, const float *dL_dworld_pts,
+                        const float *dL_dtransforms, const float *dL_dworld_normals, float *dL_dquery, float *dL_dnormals,
+                        float *dL_dlbs_offsets, float *dL_dA_pose, float *dL_doff_pose, float *dA_pose_partials,
+                        gsr_stream_t stream) {
+  return gsr::lbs_backward("gsr_lbs_backward_nj", J, P, V, query, normals, vert_ids, weights, lbs_offsets, A_big, A_pose, off_big,
+                           off_shape, off_pose, R, dL_dworld_pts, dL_dtransforms, dL_dworld_normals, dL_dquery, dL_dnormals,
+                           dL_dlbs_offsets, dL_dA_pose, dL_doff_pose, dA_pose_partials, stream);
 }
 }

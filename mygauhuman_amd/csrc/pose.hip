@@ -1,22 +1,25 @@
-// pose.hip -- SMPL pose -> 24 joint transforms, forward and backward, ONE single-wave launch each way.
+// pose.hip -- SMPL / SMPL-X pose -> J joint transforms (J <= 64: 24 for SMPL, 55 for SMPL-X), forward and backward, ONE single-wave
+// launch each way.
 //
 // Replaces the per-frame torch chain of the reference (scene/gaussian_model.py: batch_rodrigues_torch :894-912 /
 // batch_rodrigues :982-1013, the pose-refinement product rot_mats[1:] @ correct_Rs :822-825, get_rigid_transformation_torch
 // :914-944, get_transform_params_torch :947-980): ~75 tiny kernels forward (23 chained 4x4 matmuls among them) and about
 // twice that in autograd's backward, i.e. milliseconds of launch overhead for ~20 kFLOP of work.
-//   lane j < 24:  R_j = rodrigues(theta_j) (angle = |theta + 1e-8|, :989)  [ @ correct_Rs[j-1] for j >= 1 ]
+//   lane j < J:   R_j = rodrigues(theta_j) (angle = |theta + 1e-8|, :989)  [ @ correct_Rs[j-1] for j >= 1 ]
 //   lanes 0..11:  kinematic chain G_i = G_parent(i) * [R_i | J_i - J_parent(i)], joints in order (parents[i] < i)
-//   lane j < 24:  A_j = [ G_j.R | G_j.t - G_j.R J_j ]   (rest pose removed)
+//   lane j < J:   A_j = [ G_j.R | G_j.t - G_j.R J_j ]   (rest pose removed)
 // Backward = the exact adjoint of those three phases (what autograd computes for the reference chain), giving
 // dL/dposes, dL/dcorrect_Rs and dL/djoints from dL/dA and the extra dL/drot_mats of the pose blend shapes.
 #include "gsr_common.h"
 
 namespace gsr {
 
-constexpr int PJ = 24;
+constexpr int PJ = WAVE;  // most joints: one lane per joint
+constexpr int PJ_MIN = 2;
 
 struct PoseArgs {
   const float *poses, *correct_Rs, *joints;
+  int J;
   int parents[PJ];
   float *rot_mats, *A;                                 // forward outputs
   const float *g_A, *g_rot;                            // backward inputs
@@ -92,7 +95,7 @@ struct PoseLds {
 };
 
 __device__ __forceinline__ void pose_forward_phases(const PoseArgs &a, PoseLds &s, Rodrigues &rq, float *Rod, int lane) {
-  if (lane < PJ) {
+  if (lane < a.J) {
     float v[3] = {a.poses[3 * lane], a.poses[3 * lane + 1], a.poses[3 * lane + 2]};
     rodrigues_fwd(v, rq, Rod);
     float R[9];
@@ -114,7 +117,7 @@ __device__ __forceinline__ void pose_forward_phases(const PoseArgs &a, PoseLds &
   __syncthreads();
   // chain: element (r, c) of G_i on lane 4r + c
   const int r = lane / 4, c = lane % 4;
-  for (int i = 0; i < PJ; i++) {
+  for (int i = 0; i < a.J; i++) {
     if (lane < 12) {
       const float tm_0c = c < 3 ? s.R[i][c] : s.rel[i][0];
       const float tm_1c = c < 3 ? s.R[i][3 + c] : s.rel[i][1];
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_forward_kernel(const PoseArgs 
   Rodrigues rq;
   float Rod[9];
   pose_forward_phases(a, s, rq, Rod, lane);
-  if (lane < PJ) {
+  if (lane < a.J) {
     const float *G = s.G[lane];
     const float J[3] = {a.joints[3 * lane], a.joints[3 * lane + 1], a.joints[3 * lane + 2]};
     float *o = a.A + 16 * lane;
@@ -163,7 +166,7 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_backward_kernel(const PoseArgs
   float Rod[9];
   pose_forward_phases(a, s, rq, Rod, lane);
   // adjoint of A_j = [G.R | G.t - G.R J]
-  if (lane < PJ) {
+  if (lane < a.J) {
     const float *g = a.g_A + 16 * lane;
     const float J[3] = {a.joints[3 * lane], a.joints[3 * lane + 1], a.joints[3 * lane + 2]};
     float dJ[3] = {0.f, 0.f, 0.f};
@@ -183,7 +186,7 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_backward_kernel(const PoseArgs
   __syncthreads();
   // adjoint of the chain, children before parents (parents[i] < i)
   const int r = lane / 4, c = lane % 4;
-  for (int i = PJ - 1; i >= 1; i--) {
+  for (int i = a.J - 1; i >= 1; i--) {
     const int p = a.parents[i];
     float add = 0.f, dtm = 0.f;
     if (lane < 12) {
@@ -207,9 +210,9 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_backward_kernel(const PoseArgs
   }
   if (lane < 12) s_dtm[0][lane] = s.dG[0][lane];
   __syncthreads();
-  // joints: rel_i = J_i - J_parent(i); sequential scatter by one lane (24 x 3 adds)
+  // joints: rel_i = J_i - J_parent(i); sequential scatter by one lane (J x 3 adds)
   if (lane == 0) {
-    for (int i = 0; i < PJ; i++)
+    for (int i = 0; i < a.J; i++)
       for (int k = 0; k < 3; k++) {
         const float g = s_dtm[i][4 * k + 3];
         s.dJ[i][k] += g;
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_backward_kernel(const PoseArgs
       }
   }
   __syncthreads();
-  if (lane < PJ) {
+  if (lane < a.J) {
     float dR[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) dR[k] = s_dtm[lane][4 * (k / 3) + (k % 3)] + (a.g_rot ? a.g_rot[9 * lane + k] : 0.f);
@@ -246,16 +249,65 @@ __global__ __launch_bounds__(WAVE) void smpl_pose_backward_kernel(const PoseArgs
   }
 }
 
-static int check_parents(const char *who, const int *parents) {
-  if (!parents) {
-    set_error("%s: parents (host array of 24 ints) is required", who);
+static int check_joints(const char *who, int J) {
+  if (J < PJ_MIN || J > PJ) {
+    set_error("%s: J = %d joints is not supported (%d <= J <= %d: one lane per joint)", who, J, PJ_MIN, PJ);
     return GSR_EINVAL;
   }
-  for (int i = 1; i < PJ; i++)
+  return GSR_OK;
+}
+
+static int check_parents(const char *who, int J, const int *parents) {
+  if (!parents) {
+    set_error("%s: parents (host array of %d ints) is required", who, J);
+    return GSR_EINVAL;
+  }
+  for (int i = 1; i < J; i++)
     if (parents[i] < 0 || parents[i] >= i) {
       set_error("%s: parents[%d] = %d; every joint's parent must precede it", who, i, parents[i]);
       return GSR_EINVAL;
     }
+  return GSR_OK;
+}
+
+static int pose_forward(const char *who, int J, const float *poses, const float *correct_Rs, const float *joints,
+                        const int *parents_host, float *rot_mats, float *A, gsr_stream_t stream_) {
+  int rc = check_joints(who, J);
+  if (rc != GSR_OK) return rc;
+  if (!poses || !joints || !A) {
+    set_error("%s: null argument", who);
+    return GSR_EINVAL;
+  }
+  rc = check_parents(who, J, parents_host);
+  if (rc != GSR_OK) return rc;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  PoseArgs a = {};
+  a.poses = poses, a.correct_Rs = correct_Rs, a.joints = joints, a.rot_mats = rot_mats, a.A = A, a.J = J;
+  for (int i = 0; i < J; i++) a.parents[i] = i == 0 ? 0 : parents_host[i];
+  hipLaunchKernelGGL(smpl_pose_forward_kernel, dim3(1), dim3(WAVE), 0, stream, a);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+static int pose_backward(const char *who, int J, const float *poses, const float *correct_Rs, const float *joints,
+                         const int *parents_host, const float *dL_dA, const float *dL_drot_mats, float *dL_dposes,
+                         float *dL_dcorrect_Rs, float *dL_djoints, gsr_stream_t stream_) {
+  int rc = check_joints(who, J);
+  if (rc != GSR_OK) return rc;
+  if (!poses || !joints || !dL_dA) {
+    set_error("%s: null argument", who);
+    return GSR_EINVAL;
+  }
+  rc = check_parents(who, J, parents_host);
+  if (rc != GSR_OK) return rc;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  PoseArgs a = {};
+  a.poses = poses, a.correct_Rs = correct_Rs, a.joints = joints, a.J = J;
+  a.g_A = dL_dA, a.g_rot = dL_drot_mats;
+  a.d_poses = dL_dposes, a.d_correct_Rs = dL_dcorrect_Rs, a.d_joints = dL_djoints;
+  for (int i = 0; i < J; i++) a.parents[i] = i == 0 ? 0 : parents_host[i];
+  hipLaunchKernelGGL(smpl_pose_backward_kernel, dim3(1), dim3(WAVE), 0, stream, a);
+  GSR_LAUNCH_CHECK(stream, 0);
   return GSR_OK;
 }
 
@@ -264,42 +316,27 @@ static int check_parents(const char *who, const int *parents) {
 extern "C" {
 
 int gsr_smpl_pose_forward(const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
-                          float *rot_mats, float *A, gsr_stream_t stream_) {
-  using namespace gsr;
-  if (!poses || !joints || !A) {
-    set_error("gsr_smpl_pose_forward: null argument");
-    return GSR_EINVAL;
-  }
-  int rc = check_parents("gsr_smpl_pose_forward", parents_host);
-  if (rc != GSR_OK) return rc;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  PoseArgs a = {};
-  a.poses = poses, a.correct_Rs = correct_Rs, a.joints = joints, a.rot_mats = rot_mats, a.A = A;
-  for (int i = 0; i < PJ; i++) a.parents[i] = i == 0 ? 0 : parents_host[i];
-  hipLaunchKernelGGL(smpl_pose_forward_kernel, dim3(1), dim3(WAVE), 0, stream, a);
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                          float *rot_mats, float *A, gsr_stream_t stream) {
+  return gsr::pose_forward("gsr_smpl_pose_forward", 24, poses, correct_Rs, joints, parents_host, rot_mats, A, stream);
+}
+
+int gsr_body_pose_forward(int J, const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
+                          float *rot_mats, float *A, gsr_stream_t stream) {
+  return gsr::pose_forward("gsr_body_pose_forward", J, poses, correct_Rs, joints, parents_host, rot_mats, A, stream);
 }
 
 int gsr_smpl_pose_backward(const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
                            const float *dL_dA, const float *dL_drot_mats, float *dL_dposes, float *dL_dcorrect_Rs,
-                           float *dL_djoints, gsr_stream_t stream_) {
-  using namespace gsr;
-  if (!poses || !joints || !dL_dA) {
-    set_error("gsr_smpl_pose_backward: null argument");
-    return GSR_EINVAL;
-  }
-  int rc = check_parents("gsr_smpl_pose_backward", parents_host);
-  if (rc != GSR_OK) return rc;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  PoseArgs a = {};
-  a.poses = poses, a.correct_Rs = correct_Rs, a.joints = joints;
-  a.g_A = dL_dA, a.g_rot = dL_drot_mats;
-  a.d_poses = dL_dposes, a.d_correct_Rs = dL_dcorrect_Rs, a.d_joints = dL_djoints;
-  for (int i = 0; i < PJ; i++) a.parents[i] = i == 0 ? 0 : parents_host[i];
-  hipLaunchKernelGGL(smpl_pose_backward_kernel, dim3(1), dim3(WAVE), 0, stream, a);
-  GSR_LAUNCH_CHECK(stream, 0);
-  return GSR_OK;
+                           float *dL_djoints, gsr_stream_t stream) {
+  return gsr::pose_backward("gsr_smpl_pose_backward", 24, poses, correct_Rs, joints, parents_host, dL_dA, dL_drot_mats, dL_dposes,
+                            dL_dcorrect_Rs, dL_djoints, stream);
+}
+
+int gsr_body_pose_backward(int J, const float *poses, const float *correct_Rs, const float *joints, const int *parents_host,
+                           const float *dL_dA, const float *dL_drot_mats, float *dL_dposes, float *dL_dcorrect_Rs,
+                           float *dL_djoints, gsr_stream_t stream) {
+  return gsr::pose_backward("gsr_body_pose_backward", J, poses, correct_Rs, joints, parents_host, dL_dA, dL_drot_mats, dL_dposes,
+                            dL_dcorrect_Rs, dL_djoints, stream);
 }
 
 }  // extern "C"

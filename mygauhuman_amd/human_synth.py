@@ -5,7 +5,12 @@ Gaussians scattered around its vertices, ring cameras at 2.4 m looking at the bo
 step"), one target pose per view, and -- for motion_offset_flag models -- two small MLPs with the call surface of the
 reference's decoders (nets/mlp_delta_body_pose.py: pose_decoder(posevec)["Rs"] [1,23,3,3]; nets/mlp_delta_weight_lbs.py:
 lweight_offset_decoder(xyz[1,P,3]) -> [1,24,P]).  Everything is generated on the CPU from numpy's default_rng: all ranks and
-all devices see the same bits."""
+all devices see the same bits.
+
+body="smplx" makes an SMPL-X-shaped body instead (the reference's default smpl_type): V = 10,475 vertices, the 55-joint tree
+(22 body + jaw + 2 eyes + 2 x 15 hand), 20 shape columns (betas + expression), posedirs [V, 3, 486], poses [1, 165], shapes [1, 20], a
+refiner mapping the 162-d pose vector to Rs [1, 54, 3, 3] and an offset stand-in with 55 outputs.  The "smpl" body (the default) and
+its random streams are unchanged."""
 import math
 
 import numpy as np
@@ -16,24 +21,30 @@ from .lbs import batch_rodrigues
 from .scene_model import HumanGaussianModel
 
 PARENTS = np.array([-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21], np.int64)
+PARENTS_SMPLX = np.array([-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 15, 15, 15, 20, 25, 26, 20, 28,
+                          29, 20, 31, 32, 20, 34, 35, 20, 37, 38, 21, 40, 41, 21, 43, 44, 21, 46, 47, 21, 49, 50, 21, 52, 53], np.int64)
+# body -> (vertices, joints, shape columns, parents)
+BODIES = {"smpl": (6890, 24, 10, PARENTS), "smplx": (10475, 55, 20, PARENTS_SMPLX)}
 
 
 class PoseRefiner(torch.nn.Module):
-    """posevec [1,69] -> {"Rs": [1,23,3,3]}: a small MLP whose output (23 axis-angle corrections, initialised near zero) goes
-    through rodrigues, like BodyPoseRefiner."""
+    """posevec [1,3(J-1)] -> {"Rs": [1,J-1,3,3]}: a small MLP whose output (J - 1 axis-angle corrections, initialised near zero) goes
+    through rodrigues, like BodyPoseRefiner.  J = 24: 69 -> 23; J = 55 (SMPL-X): 162 -> 54."""
 
-    def __init__(self, width=128, seed=0):
+    def __init__(self, width=128, seed=0, joints=24):
         super().__init__()
         g = torch.Generator().manual_seed(seed)
-        self.w1 = torch.nn.Parameter(torch.randn((69, width), generator=g) / math.sqrt(69.0))
+        n = 3 * (joints - 1)
+        self.n = n
+        self.w1 = torch.nn.Parameter(torch.randn((n, width), generator=g) / math.sqrt(float(n)))
         self.b1 = torch.nn.Parameter(torch.zeros(width))
-        self.w2 = torch.nn.Parameter(1e-2 * torch.randn((width, 69), generator=g) / math.sqrt(width))
-        self.b2 = torch.nn.Parameter(torch.zeros(69))
+        self.w2 = torch.nn.Parameter(1e-2 * torch.randn((width, n), generator=g) / math.sqrt(width))
+        self.b2 = torch.nn.Parameter(torch.zeros(n))
 
     def forward(self, posevec):
-        h = torch.relu(posevec.reshape(1, 69) @ self.w1 + self.b1)
-        rv = (h @ self.w2 + self.b2).reshape(23, 3)
-        return {"Rs": batch_rodrigues(rv).reshape(1, 23, 3, 3)}
+        h = torch.relu(posevec.reshape(1, self.n) @ self.w1 + self.b1)
+        rv = (h @ self.w2 + self.b2).reshape(self.n // 3, 3)
+        return {"Rs": batch_rodrigues(rv).reshape(1, self.n // 3, 3, 3)}
 
 
 class LbsOffsetDecoder(torch.nn.Module):
@@ -48,26 +59,35 @@ class LbsOffsetDecoder(torch.nn.Module):
     a 3- or 24-wide side spends the frame in rocBLAS' skinny-GEMM kernels: a 3-64-24 MLP on 200k points measured 1.2 ms of two
     rocBLAS launches per frame, more than the whole render() frame -- which is why the stand-in is affine.)"""
 
-    def __init__(self, seed=1):
+    def __init__(self, seed=1, joints=24):
         super().__init__()
         g = torch.Generator().manual_seed(seed)
-        self.A = torch.nn.Parameter(0.05 * torch.randn((3, 24), generator=g))
-        self.b = torch.nn.Parameter(torch.zeros(24))
+        self.A = torch.nn.Parameter(0.05 * torch.randn((3, joints), generator=g))
+        self.b = torch.nn.Parameter(torch.zeros(joints))
 
     def forward(self, xyz):
         x = xyz[0]
-        out = self.b + x[:, 0:1] * self.A[0] + x[:, 1:2] * self.A[1] + x[:, 2:3] * self.A[2]   # [P, 24]
+        out = self.b + x[:, 0:1] * self.A[0] + x[:, 1:2] * self.A[1] + x[:, 2:3] * self.A[2]   # [P, J]
         return out.t()[None]
 
 
-def body_arrays(V=6890, seed=0):
+def body_arrays(V=None, seed=0, body="smpl"):
+    """The body tables as numpy arrays (posedirs in gaussian_model.py's [V, 3, 9(J-1)] layout); V = None: the body's own count."""
+    nv, nj, ns, _ = BODIES[body]
+    V = nv if V is None else V
     rng = np.random.default_rng(seed)
     vt = rng.uniform(-1, 1, (V, 3)).astype(np.float32) * np.array([0.45, 0.9, 0.15], np.float32)
-    J = rng.uniform(0, 1, (24, V)).astype(np.float32)
-    w = rng.uniform(0, 1, (V, 24)).astype(np.float32) ** 4
-    return dict(v_template=vt, shapedirs=rng.normal(0, 0.01, (V, 3, 10)).astype(np.float32),
-                posedirs=rng.normal(0, 0.001, (V, 3, 207)).astype(np.float32), J_regressor=J / J.sum(1, keepdims=True),
+    J = rng.uniform(0, 1, (nj, V)).astype(np.float32)
+    w = rng.uniform(0, 1, (V, nj)).astype(np.float32) ** 4
+    return dict(v_template=vt, shapedirs=rng.normal(0, 0.01, (V, 3, ns)).astype(np.float32),
+                posedirs=rng.normal(0, 0.001, (V, 3, 9 * (nj - 1))).astype(np.float32), J_regressor=J / J.sum(1, keepdims=True),
                 weights=(w / w.sum(1, keepdims=True)).astype(np.float32))
+
+
+def kintree_table(body="smpl"):
+    """[2, J] int64: parents (entry 0 = -1) over joint indices, the layout of the SMPL / SMPL-X model files."""
+    parents = BODIES[body][3]
+    return np.stack([parents, np.arange(parents.shape[0])])
 
 
 def gaussian_arrays(body, P, seed=0, scale=0.006):
@@ -82,38 +102,42 @@ def gaussian_arrays(body, P, seed=0, scale=0.006):
 
 def view_camera(body, W, H, view, n_views=8, device="cuda", radius=2.4, fov_deg=50.0, pose_scale=0.15):
     """Ring camera `view` of n_views (view 0 looks along +z from z = -radius, like tools/render_bench.py) with ITS OWN target pose
-    and shape (seeded by the view index) and the shared big pose."""
+    and shape (seeded by the view index) and the shared big pose.  poses [1, 3J] and shapes [1, shape columns] follow `body`."""
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
     cam_np = cameras.ring_camera(W, H, view % n_views, n_views, radius=radius, fov_deg=fov_deg)
+    nj, ns = body["weights"].shape[1], body["shapedirs"].shape[2]
     rng = np.random.default_rng(1000 + view)
-    sp = dict(poses=d(rng.normal(0, pose_scale, (1, 72))), shapes=d(rng.normal(0, 0.5, (1, 10))), R=d(np.eye(3)),
+    sp = dict(poses=d(rng.normal(0, pose_scale, (1, 3 * nj))), shapes=d(rng.normal(0, 0.5, (1, ns))), R=d(np.eye(3)),
               Th=d(np.zeros((1, 3))))
-    bp = dict(poses=d(np.zeros((1, 72))), shapes=d(np.zeros((1, 10))), R=d(np.eye(3)), Th=d(np.zeros((1, 3))))
+    bp = dict(poses=d(np.zeros((1, 3 * nj))), shapes=d(np.zeros((1, ns))), R=d(np.eye(3)), Th=d(np.zeros((1, 3))))
     cam = cameras.ViewCamera(cam_np, device, sp, bp, d(body["v_template"]))
     cam.cam_np = cam_np
     return cam
 
 
-def build(P, V=6890, device="cuda", seed=0, motion=False, sh_degree=3, decoder="affine"):
+def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="affine", body="smpl"):
     """(model, body arrays).  model.SMPL_NEUTRAL holds the body tables as device tensors; motion=True attaches the two decoders
-    (decoder = "affine": the 96-parameter stand-in; "reference_size": nets.FusedLBSOffsetDecoder -- the reference network's layers,
-    random init -- on the fused kernels; "reference_size_torch": the same module in torch ops)."""
+    (decoder = "affine": the 3 x J stand-in; "reference_size": nets.FusedLBSOffsetDecoder -- the reference network's layers,
+    random init -- on the fused kernels (torch ops at J != 24); "reference_size_torch": the same module in torch ops).
+    body: "smpl" (default, 24 joints) or "smplx" (55 joints); V = None: the body's own vertex count."""
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
-    body = body_arrays(V, seed)
+    kind = body
+    body = body_arrays(V, seed, kind)
+    nj = BODIES[kind][1]
     smpl = {k: d(v) for k, v in body.items()}
-    smpl["kintree_table"] = torch.from_numpy(np.stack([PARENTS, np.arange(24)])).to(device)
+    smpl["kintree_table"] = torch.from_numpy(kintree_table(kind)).to(device)
     model = HumanGaussianModel.from_arrays(gaussian_arrays(body, P, seed), sh_degree, smpl=smpl, motion_offset_flag=motion,
                                            device=device, seed=seed)
     if motion:
-        model.pose_decoder = PoseRefiner().to(device)
+        model.pose_decoder = PoseRefiner(joints=nj).to(device)
         if decoder in ("reference_size", "reference_size_torch"):
             from .nets import FusedLBSOffsetDecoder
             torch.manual_seed(seed + 7)
-            net = FusedLBSOffsetDecoder().to(device)
+            net = FusedLBSOffsetDecoder(nj).to(device)
             with torch.no_grad():
                 net.bw_fc.weight.mul_(0.05)      # small offsets around the SMPL weights, like a network early in training
-            net.use_fused = decoder == "reference_size"
+            net.use_fused = decoder == "reference_size" and nj == net.FUSED_BONES
             model.lweight_offset_decoder = net
         else:
-            model.lweight_offset_decoder = LbsOffsetDecoder().to(device)
+            model.lweight_offset_decoder = LbsOffsetDecoder(joints=nj).to(device)
     return model, body

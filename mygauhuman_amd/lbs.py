@@ -4,9 +4,12 @@ Mirrors GaussianModel.coarse_deform_c2source (scene/gaussian_model.py:768-872: s
 self.SMPL_NEUTRAL).  Its helpers (:894-1013: rodrigues, rigid transformation chain, transform parameters) run as ONE
 single-wave HIP kernel each way (csrc/pose.hip, smpl_pose_transforms below); the plain-torch formulation of that chain lives
 with the tests (tests/torch_reference.py) as its checker.  The per-vertex blend-shape offsets are HIP GEMVs.  Everything per POINT
-(nearest SMPL vertex, weight softmax, 24-way blends, 3x3 inverse, offsets, posing, world transform) is ONE HIP
-kernel forward (gsr_lbs_forward) and ONE backward (gsr_lbs_backward) behind a torch.autograd.Function, instead of
-~40 torch kernels + KNN_CUDA + an autograd graph over [P, 24, 16] intermediates.
+(nearest SMPL vertex, weight softmax, J-way blends, 3x3 inverse, offsets, posing, world transform) is ONE HIP
+kernel forward (gsr_lbs_forward_nj) and ONE backward (gsr_lbs_backward_nj) behind a torch.autograd.Function, instead of
+~40 torch kernels + KNN_CUDA + an autograd graph over [P, J, 16] intermediates.
+
+The joint count J is the body model's: smpl["weights"].shape[-1] -- 24 for SMPL, 55 for SMPL-X (whose `poses` are [1, 165], `shapes`
+[1, 20] = betas + expression, posedirs [V, 3, 486]) -- and the kinematic tree is smpl["kintree_table"][0].
 """
 import ctypes as C
 
@@ -71,15 +74,15 @@ def _ident3(dtype, device):
 
 
 def pose_offsets(smpl, rot_mats):
-    """(R[1:] - I).flatten() [1,207] @ posedirs^T -> per-vertex offsets [V,3] (gaussian_model.py:805-811,827-839): one
-    HBM-streaming HIP GEMV (rocBLAS needs 60 us for this 17 MB product).  No CPU / torch fallback."""
+    """(R[1:] - I).flatten() [1,9(J-1)] @ posedirs^T -> per-vertex offsets [V,3] (gaussian_model.py:805-811,827-839): one
+    HBM-streaming HIP GEMV (rocBLAS needs 60 us for SMPL's 17 MB product; SMPL-X's is 61 MB).  No CPU / torch fallback."""
     posedirs = smpl["posedirs"]
     V = smpl["v_template"].shape[0]
     ident = _ident3(rot_mats.dtype, rot_mats.device)
     feat = (rot_mats[:, 1:] - ident).reshape(rot_mats.shape[0], -1)
     pd = posedirs.reshape(V * 3, -1)
-    if not (pd.is_cuda and feat.shape[0] == 1 and pd.shape[1] <= 256 and pd.dtype == torch.float32):
-        raise RuntimeError("pose_offsets: float32 posedirs [V*3, K <= 256] on a HIP device and batch size 1 are required")
+    if not (pd.is_cuda and feat.shape[0] == 1 and pd.shape[1] <= 512 and pd.dtype == torch.float32):
+        raise RuntimeError("pose_offsets: float32 posedirs [V*3, K <= 512] on a HIP device and batch size 1 are required")
     return _RowGemv.apply(pd, feat[0]).view(V, 3)
 
 
@@ -128,8 +131,8 @@ _CONSTANTS = _FrameConstants()
 
 
 def parents_host(smpl):
-    """Kinematic-tree parents as a host tuple, read from the device once per SMPL dict (the reference indexes the device
-    tensor joint by joint: 23 blocking reads per chain)."""
+    """Kinematic-tree parents as a host tuple of J entries, read from the device once per SMPL dict (the reference indexes the
+    device tensor joint by joint: J - 1 blocking reads per chain)."""
     cached = smpl.get("_parents_host")
     if cached is None:
         cached = tuple(int(v) for v in smpl["kintree_table"][0].tolist())
@@ -138,23 +141,25 @@ def parents_host(smpl):
 
 
 class _SmplPose(torch.autograd.Function):
-    """poses [72] (+ correct_Rs [23,3,3]) + joints [24,3] -> (rot_mats [24,3,3], A [24,4,4]); csrc/pose.hip."""
+    """poses [3J] (+ correct_Rs [J-1,3,3]) + joints [J,3] -> (rot_mats [J,3,3], A [J,4,4]); csrc/pose.hip.  J = len(parents):
+    24 for SMPL, 55 for SMPL-X."""
 
     @staticmethod
     def forward(ctx, poses, correct_Rs, joints, parents):
         if not poses.is_cuda:
             raise RuntimeError("SMPL pose kernel: tensors must live on a HIP device (no CPU path)")
         dev, f32 = poses.device, torch.float32
+        J = len(parents)
         c = lambda t: None if t is None else t.detach().contiguous().float()  # noqa: E731
-        poses_c, cr, j = c(poses).reshape(72), c(correct_Rs), c(joints).reshape(24, 3)
+        poses_c, cr, j = c(poses).reshape(3 * J), c(correct_Rs), c(joints).reshape(J, 3)
         if cr is not None:
-            cr = cr.reshape(23, 9)
-        par = (C.c_int * 24)(*parents)
-        rot = torch.empty((24, 3, 3), dtype=f32, device=dev)
-        A = torch.empty((24, 4, 4), dtype=f32, device=dev)
+            cr = cr.reshape(J - 1, 9)
+        par = (C.c_int * J)(*parents)
+        rot = torch.empty((J, 3, 3), dtype=f32, device=dev)
+        A = torch.empty((J, 4, 4), dtype=f32, device=dev)
         with torch.cuda.device(dev):
-            check(lib.gsr_smpl_pose_forward(ptr(poses_c), ptr(cr), ptr(j), par, ptr(rot), ptr(A),
-                                            torch.cuda.current_stream(dev).cuda_stream), "gsr_smpl_pose_forward")
+            check(lib.gsr_body_pose_forward(J, ptr(poses_c), ptr(cr), ptr(j), par, ptr(rot), ptr(A),
+                                            torch.cuda.current_stream(dev).cuda_stream), "gsr_body_pose_forward")
         ctx.has_cr = cr is not None
         ctx.save_for_backward(*([poses_c, j] + ([cr] if cr is not None else [])))
         ctx.meta = (parents, poses.shape, None if correct_Rs is None else correct_Rs.shape, joints.shape)
@@ -167,34 +172,35 @@ class _SmplPose(torch.autograd.Function):
         cr = saved[2] if ctx.has_cr else None
         parents, p_shape, c_shape, j_shape = ctx.meta
         dev, f32 = poses.device, torch.float32
-        par = (C.c_int * 24)(*parents)
+        J = len(parents)
+        par = (C.c_int * J)(*parents)
         need_p, need_c, need_j = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and ctx.has_cr, ctx.needs_input_grad[2]
-        d_p = torch.empty((72,), dtype=f32, device=dev) if need_p else None
-        d_c = torch.empty((23, 9), dtype=f32, device=dev) if need_c else None
-        d_j = torch.empty((24, 3), dtype=f32, device=dev) if need_j else None
-        g_A = torch.zeros((24, 4, 4), dtype=f32, device=dev) if g_A is None else g_A.contiguous().float()
+        d_p = torch.empty((3 * J,), dtype=f32, device=dev) if need_p else None
+        d_c = torch.empty((J - 1, 9), dtype=f32, device=dev) if need_c else None
+        d_j = torch.empty((J, 3), dtype=f32, device=dev) if need_j else None
+        g_A = torch.zeros((J, 4, 4), dtype=f32, device=dev) if g_A is None else g_A.contiguous().float()
         g_rot = None if g_rot is None else g_rot.contiguous().float()
         with torch.cuda.device(dev):
-            check(lib.gsr_smpl_pose_backward(ptr(poses), ptr(cr), ptr(j), par, ptr(g_A), ptr(g_rot), ptr(d_p), ptr(d_c), ptr(d_j),
-                                             torch.cuda.current_stream(dev).cuda_stream), "gsr_smpl_pose_backward")
+            check(lib.gsr_body_pose_backward(J, ptr(poses), ptr(cr), ptr(j), par, ptr(g_A), ptr(g_rot), ptr(d_p), ptr(d_c), ptr(d_j),
+                                             torch.cuda.current_stream(dev).cuda_stream), "gsr_body_pose_backward")
         return (None if d_p is None else d_p.view(p_shape), None if d_c is None else d_c.view(c_shape),
                 None if d_j is None else d_j.view(j_shape), None)
 
 
 def smpl_pose_transforms(smpl, params, correct_Rs=None):
     """HIP counterpart of batch_rodrigues + get_transform_params_torch for batch size 1:
-    returns (A [1,24,4,4], rot_mats [1,24,3,3], joints [1,24,3])."""
+    returns (A [1,J,4,4], rot_mats [1,J,3,3], joints [1,J,3])."""
     betas = params["shapes"]
     nb = int(betas.shape[-1])
     # joints = J_regressor (v_template + shapedirs beta) = J_template + J_shapedirs beta: the two regressed tables are
-    # constants of the SMPL model and are cached on the dict (the per-frame [24 x 6890] x [6890 x 3] product is a one-tile,
-    # K = 6890 rocBLAS launch of 60 us)
+    # constants of the SMPL model and are cached on the dict (the per-frame [J x V] x [V x 3] product is a one-tile,
+    # K = V rocBLAS launch of 60 us)
     cache = smpl.get("_joint_tables")
     sig = (nb,) + tuple(_FrameConstants._sig(smpl[k]) for k in ("J_regressor", "v_template", "shapedirs"))
     if cache is None or cache[0] != sig:
         with torch.no_grad():
-            Jt = torch.matmul(smpl["J_regressor"], smpl["v_template"])                                       # [24, 3]
-            Js = torch.einsum("jv,vcl->jcl", smpl["J_regressor"], smpl["shapedirs"][..., :nb].float())       # [24, 3, nb]
+            Jt = torch.matmul(smpl["J_regressor"], smpl["v_template"])                                       # [J, 3]
+            Js = torch.einsum("jv,vcl->jcl", smpl["J_regressor"], smpl["shapedirs"][..., :nb].float())       # [J, 3, nb]
         cache = (sig, Jt.contiguous(), Js.contiguous())
         smpl["_joint_tables"] = cache
     # (a subject's betas are the same tensor frame after frame: the small product is cached on it)
@@ -268,21 +274,24 @@ class _LBSDeform(torch.autograd.Function):
         if not query.is_cuda:
             raise RuntimeError("LBS deform: tensors must live on a HIP device (no CPU path)")
         dev, f32 = query.device, torch.float32
-        P, V = query.shape[0], smpl_verts.shape[0]
+        P, V, J = query.shape[0], smpl_verts.shape[0], weights.shape[-1]
         c = lambda t: None if t is None else t.detach().contiguous().float()  # noqa: E731
+        if weights.dim() != 2 or weights.shape[0] < V or (lbs_offsets is not None and tuple(lbs_offsets.shape) != (P, J)):
+            raise ValueError(f"LBS deform: weights [>= {V}, J] and lbs_offsets [P, J] = [{P}, {J}] expected, got "
+                             f"{tuple(weights.shape)} and {None if lbs_offsets is None else tuple(lbs_offsets.shape)}")
         query_c, normals_c, loff = c(query), c(normals), c(lbs_offsets)
-        A_big_c, A_pose_c = c(A_big).reshape(24, 16), c(A_pose).reshape(24, 16)
+        A_big_c, A_pose_c = c(A_big).reshape(J, 16), c(A_pose).reshape(J, 16)
         ob, os_, op = c(off_big), c(off_shape), c(off_pose)
         R_c, Th_c, sv, w = c(R).reshape(3, 3), c(Th).reshape(3), c(smpl_verts), c(weights)
         vert_ids = torch.empty((P,), dtype=torch.int32, device=dev)
         # lean: the caller (render()) only consumes world points / transforms / normals: skip 120 B per point of stores
-        bweights = None if lean else torch.empty((P, 24), dtype=f32, device=dev)
+        bweights = None if lean else torch.empty((P, J), dtype=f32, device=dev)
         smpl_pts = None if lean else torch.empty((P, 3), dtype=f32, device=dev)
         world_pts = torch.empty((P, 3), dtype=f32, device=dev)
         transforms = torch.empty((P, 3, 3), dtype=f32, device=dev)
         translation = None if lean else torch.empty((P, 3), dtype=f32, device=dev)
         world_normals = torch.empty((P, 3), dtype=f32, device=dev) if normals is not None else None
-        args = (P, V, ptr(query_c), ptr(normals_c), ptr(sv), ptr(w), ptr(loff), ptr(A_big_c), ptr(A_pose_c), ptr(ob), ptr(os_),
+        args = (J, P, V, ptr(query_c), ptr(normals_c), ptr(sv), ptr(w), ptr(loff), ptr(A_big_c), ptr(A_pose_c), ptr(ob), ptr(os_),
                 ptr(op), ptr(R_c), ptr(Th_c), ptr(vert_ids), ptr(bweights), ptr(smpl_pts), ptr(world_pts), ptr(transforms),
                 ptr(translation), ptr(world_normals))
         with torch.cuda.device(dev):
@@ -297,12 +306,12 @@ class _LBSDeform(torch.autograd.Function):
                     if not built:
                         check(lib.gsr_lbs_grid_build(V, ptr(sv), ptr(ws), ws.numel(), stream), "gsr_lbs_grid_build")
                     nn, valid = _GRIDS.nn_cache(smpl_verts, P)
-                    check(lib.gsr_lbs_forward_cached(*args, ptr(ws), ws.numel(), ptr(nn), nn.numel(), int(valid), stream),
-                          "gsr_lbs_forward_cached")
+                    check(lib.gsr_lbs_forward_cached_nj(*args, ptr(ws), ws.numel(), ptr(nn), nn.numel(), int(valid), stream),
+                          "gsr_lbs_forward_cached_nj")
                 else:
-                    check(lib.gsr_lbs_forward_grid(*args, ptr(ws), ws.numel(), int(built), stream), "gsr_lbs_forward_grid")
+                    check(lib.gsr_lbs_forward_grid_nj(*args, ptr(ws), ws.numel(), int(built), stream), "gsr_lbs_forward_grid_nj")
             else:
-                check(lib.gsr_lbs_forward(*args, stream), "gsr_lbs_forward")
+                check(lib.gsr_lbs_forward_nj(*args, stream), "gsr_lbs_forward_nj")
         ctx.save_for_backward(query_c, normals_c, loff, A_big_c, A_pose_c, ob, os_, op, R_c, vert_ids, w)
         ctx.shapes = (A_pose.shape, off_pose.shape, V)
         e = torch.empty(0, device=dev)
@@ -317,26 +326,26 @@ class _LBSDeform(torch.autograd.Function):
         query, normals, loff, A_big, A_pose, ob, os_, op, R, vert_ids, w = ctx.saved_tensors
         A_shape, off_shape_, V = ctx.shapes
         dev, f32 = query.device, torch.float32
-        P = query.shape[0]
+        P, J = query.shape[0], w.shape[-1]
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
         g_world, g_transforms = c(g_world), c(g_transforms)
         g_normals = c(g_normals) if (normals is not None and g_normals is not None and g_normals.numel()) else None
         d_query = torch.empty((P, 3), dtype=f32, device=dev)
         d_normals = torch.empty((P, 3), dtype=f32, device=dev) if normals is not None else None
-        d_loff = torch.empty((P, 24), dtype=f32, device=dev) if loff is not None else None
-        # A_pose / off_pose gradients only when the pose path is trainable (pose-refinement MLP): their reductions are atomics
-        # of every workgroup onto 288 + 3V addresses
+        d_loff = torch.empty((P, J), dtype=f32, device=dev) if loff is not None else None
+        # A_pose / off_pose gradients only when the pose path is trainable (pose-refinement MLP): per-workgroup partials of the
+        # 12 J entries of dA_pose (reduced below) and atomics onto 3V addresses
         need_A, need_off = ctx.needs_input_grad[4], ctx.needs_input_grad[7]
-        d_A = torch.zeros((24, 16), dtype=f32, device=dev) if need_A else None
-        partials = torch.empty((lib.gsr_lbs_backward_workgroups(P), 24 * 12), dtype=f32, device=dev) if need_A else None
+        d_A = torch.zeros((J, 16), dtype=f32, device=dev) if need_A else None
+        partials = torch.empty((lib.gsr_lbs_backward_workgroups(P), J * 12), dtype=f32, device=dev) if need_A else None
         d_off = torch.zeros((V, 3), dtype=f32, device=dev) if need_off else None
         with torch.cuda.device(dev):
-            check(lib.gsr_lbs_backward(P, V, ptr(query), ptr(normals), ptr(vert_ids), ptr(w), ptr(loff), ptr(A_big), ptr(A_pose),
+            check(lib.gsr_lbs_backward_nj(J, P, V, ptr(query), ptr(normals), ptr(vert_ids), ptr(w), ptr(loff), ptr(A_big), ptr(A_pose),
                                        ptr(ob), ptr(os_), ptr(op), ptr(R), ptr(g_world), ptr(g_transforms), ptr(g_normals),
                                        ptr(d_query), ptr(d_normals), ptr(d_loff), ptr(d_A), ptr(d_off), ptr(partials),
-                                       torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_backward")
-        if need_A:  # per-workgroup sums -> rows 0..2 of the 24 4x4 gradients (row 3 of A is constant)
-            d_A.view(24, 4, 4)[:, :3, :] = partials.sum(0).view(24, 3, 4)
+                                       torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_backward_nj")
+        if need_A:  # per-workgroup sums -> rows 0..2 of the J 4x4 gradients (row 3 of A is constant)
+            d_A.view(J, 4, 4)[:, :3, :] = partials.sum(0).view(J, 3, 4)
         return (d_query, d_normals, d_loff, None, None if d_A is None else d_A.view(A_shape), None, None,
                 None if d_off is None else d_off.view(off_shape_), None, None, None, None, None)
 
@@ -353,7 +362,8 @@ def coarse_deform_c2source(smpl, query_pts, params, t_params, t_vertices, lbs_we
                            return_transl=False, normals=None, lean=False):
     """Drop-in for GaussianModel.coarse_deform_c2source (batch size 1): same arguments after `smpl`
     (= self.SMPL_NEUTRAL as device tensors) and the same 6-tuple
-    (smpl_src_pts[1,P,3], world_src_pts[1,P,3], bweights[1,P,24], transforms[1,P,3,3], translation|None, world_normals)."""
+    (smpl_src_pts[1,P,3], world_src_pts[1,P,3], bweights[1,P,J], transforms[1,P,3,3], translation|None, world_normals), J =
+    smpl["weights"].shape[-1] (24 SMPL, 55 SMPL-X)."""
     assert query_pts.shape[0] == 1, "batch size 1 (like every call site of the reference)"
     # big pose -> T pose, T pose -> target pose: one single-wave kernel each (csrc/pose.hip)
     # the big-pose side depends on the camera's big_pose_smpl_param alone, the shape offsets on the subject's betas: both are
@@ -373,10 +383,10 @@ def coarse_deform_c2source(smpl, query_pts, params, t_params, t_vertices, lbs_we
                                lambda: shape_offsets(smpl, shapes_in.to(query_pts.device)), smpl_keys=("shapedirs",))
     off_pose = pose_offsets(smpl, rot_mats)
     # (batch size 1: reshape, not [0] -- the backward of a select materialises a zero [1, P, 3] tensor and copies into it)
-    P_ = query_pts.shape[1]
+    P_, J = query_pts.shape[1], smpl["weights"].shape[-1]
     o = lbs_deform(query_pts.reshape(P_, 3), None if normals is None else normals.reshape(P_, 3),
                    None if lbs_weights is None else lbs_weights.reshape(P_, -1),
-                   A_big.reshape(24, 4, 4), A_pose.reshape(24, 4, 4), off_big, off_shape, off_pose, R.reshape(3, 3), Th.reshape(-1)[:3],
+                   A_big.reshape(J, 4, 4), A_pose.reshape(J, 4, 4), off_big, off_shape, off_pose, R.reshape(3, 3), Th.reshape(-1)[:3],
                    t_vertices.reshape(-1, 3), smpl["weights"], lean=lean and not return_transl)
     translation = o["translation"][None] if return_transl else None
     wn = None if o["world_normals"] is None else o["world_normals"][None]
@@ -385,9 +395,9 @@ def coarse_deform_c2source(smpl, query_pts, params, t_params, t_vertices, lbs_we
 
 def smplx_lbs(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights):
     """The vendored smplx `lbs()` of the reference (smplx/lbs.py:156-252, fork returns 4 values): BASELINE config 1.
-    Device-agnostic torch, batch-first: betas [B,NB], pose [B,72], v_template [1,V,3] or [V,3], shapedirs [V,3,NB],
-    posedirs [207, V*3], J_regressor [24,V], parents [24], lbs_weights [V,24] -> (verts [B,V,3], J_transformed [B,24,3],
-    A [B,24,4,4], T [B,V,4,4])."""
+    Device-agnostic torch, batch-first, any joint count J (24 SMPL, 55 SMPL-X): betas [B,NB], pose [B,3J], v_template [1,V,3] or
+    [V,3], shapedirs [V,3,>=NB], posedirs [9(J-1), V*3], J_regressor [J,V], parents [J], lbs_weights [V,J] -> (verts [B,V,3],
+    J_transformed [B,J,3], A [B,J,4,4], T [B,V,4,4])."""
     B = max(betas.shape[0], pose.shape[0])
     vt = v_template if v_template.dim() == 3 else v_template[None]
     v_shaped = vt + torch.einsum("bl,mkl->bmk", betas, shapedirs[..., :betas.shape[-1]])

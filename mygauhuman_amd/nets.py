@@ -10,6 +10,10 @@ spends in skinny fp32 GEMMs and 100-MB elementwise kernels.  Here forward() is O
 in registers, the accuracy of the torch ops) and the backward two (the forward again + dh = W^T dZ chained the same way; the
 weight gradients as products over the points).  render() hands the positions in DETACHED (:104): a `pts` that requires grad takes
 the same arithmetic in torch ops instead (forward_torch).  Tensors must live on the GPU: there is no CPU path for the fused kernels.
+
+The fused kernels are built for the 24 SMPL joints (csrc/mlp.hip packs the output layer as one 32-row tile).  Any other bone count --
+SMPL-X's 55 -- builds the reference's layer shapes (bw_fc = Conv1d(128, total_bones)) and runs forward_torch: the reference's
+arithmetic in torch ops, use_fused False.
 """
 import ctypes as C
 
@@ -34,17 +38,20 @@ def positional_embedding(x):
 
 
 class FusedLBSOffsetDecoder(torch.nn.Module):
+    FUSED_BONES = 24   # the output width the fused kernels are built for
+
     def __init__(self, total_bones=24):
         super().__init__()
-        if total_bones != 24:
-            raise ValueError("FusedLBSOffsetDecoder: built for the 24 SMPL joints")
+        if total_bones < 1:
+            raise ValueError(f"FusedLBSOffsetDecoder: total_bones = {total_bones}")
         self.total_bones = total_bones
         E, W = 3 + 3 * 2 * _OCTAVES, 128
         self.bw_linears = torch.nn.ModuleList([torch.nn.Conv1d(E, W, 1), torch.nn.Conv1d(W, W, 1), torch.nn.Conv1d(W, W, 1),
                                                torch.nn.Conv1d(W + E, W, 1)])
         self.bw_fc = torch.nn.Conv1d(W, total_bones, 1)
         self._packed, self._packed_key = None, None
-        self.use_fused = True   # False: the same arithmetic in torch ops (forward_torch), for comparison
+        # False: the same arithmetic in torch ops (forward_torch), for comparison -- and the only path at total_bones != 24
+        self.use_fused = total_bones == self.FUSED_BONES
 
     def _layers(self):
         return list(self.bw_linears) + [self.bw_fc]
@@ -72,8 +79,8 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
         return torch.addmm(self.bw_fc.bias, h, self.bw_fc.weight[:, :, 0].t()).t()[None]
 
     def forward(self, pts):
-        """pts [1, P, 3] -> [1, 24, P]."""
-        if not self.use_fused or (torch.is_grad_enabled() and pts.requires_grad):
+        """pts [1, P, 3] -> [1, total_bones, P]."""
+        if not self.use_fused or self.total_bones != self.FUSED_BONES or (torch.is_grad_enabled() and pts.requires_grad):
             return self.forward_torch(pts)   # (an input gradient is not built: render() detaches the positions)
         if not pts.is_cuda:
             raise RuntimeError("FusedLBSOffsetDecoder: tensors must live on a HIP device (no CPU path)")
