@@ -647,6 +647,18 @@ int gsr_debug_lbs_offset_mlp_forward_bf16x3(int P, const float *xyz, const float
 size_t gsr_lbs_offset_mlp_backward_workspace_floats(int P);
 int gsr_lbs_offset_mlp_backward(int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
                                 float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream);
+/* Bone-count variants of the six entry points above: the same arguments after a leading nb, the output width of bw_fc -- 24 (SMPL:
+ * exactly the entry points without _nb) or 55 (SMPL-X: bw_fc [55][128] and [55], out and dL_dout [P][55]).  Any other nb is refused
+ * (GSR_EINVAL, or 0 from the two size queries; gsr_last_error() names it) before any other argument or the device is looked at.  A
+ * packed buffer holds one bone count: gsr_lbs_offset_mlp_packed_floats_nb(55) is larger than (24), and the two are not
+ * interchangeable.  gsr_lbs_offset_mlp_set_precision covers both counts. */
+size_t gsr_lbs_offset_mlp_packed_floats_nb(int nb);
+int gsr_lbs_offset_mlp_pack_nb(int nb, const float *const *weights, const float *const *biases, float *packed, gsr_stream_t stream);
+int gsr_lbs_offset_mlp_forward_nb(int nb, int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream);
+int gsr_debug_lbs_offset_mlp_forward_bf16x3_nb(int nb, int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream);
+size_t gsr_lbs_offset_mlp_backward_workspace_floats_nb(int nb, int P);
+int gsr_lbs_offset_mlp_backward_nb(int nb, int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
+                                   float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,8 @@ SYMBOLS = [
     "gsr_dist2_workspace_bytes", "gsr_dist2", "gsr_sort_workspace_bytes", "gsr_sort_pairs_u64",
     "gsr_sort_pairs_u32", "gsr_lbs_forward", "gsr_lbs_backward", "gsr_lbs_backward_workgroups", "gsr_lbs_workspace_bytes", "gsr_lbs_grid_build", "gsr_lbs_forward_grid", "gsr_lbs_forward_cached", "gsr_lbs_nn_cache_bytes", "gsr_smpl_pose_forward", "gsr_smpl_pose_backward", "gsr_sh_view_pack", "gsr_sh_grad_from_views", "gsr_sh_view_pack_posed", "gsr_sh_grad_from_views_posed", "gsr_step_status", "gsr_step_finish", "gsr_knn_self", "gsr_knn_nearest", "gsr_gather_rows", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_gemv_rows", "gsr_gemv_rows_t", "gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_lbs_offset_mlp_packed_floats", "gsr_lbs_offset_mlp_pack", "gsr_lbs_offset_mlp_forward", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward", "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_set_precision",
     "gsr_lbs_forward_nj", "gsr_lbs_forward_grid_nj", "gsr_lbs_forward_cached_nj", "gsr_lbs_backward_nj", "gsr_body_pose_forward",
-    "gsr_body_pose_backward",
+    "gsr_body_pose_backward", "gsr_lbs_offset_mlp_packed_floats_nb", "gsr_lbs_offset_mlp_pack_nb", "gsr_lbs_offset_mlp_forward_nb",
+    "gsr_debug_lbs_offset_mlp_forward_bf16x3_nb", "gsr_lbs_offset_mlp_backward_workspace_floats_nb", "gsr_lbs_offset_mlp_backward_nb",
 ]
 
 GSR_OK = 0
@@ -180,6 +181,11 @@ def _load():
     lib.gsr_lbs_offset_mlp_backward_workspace_floats.restype = C.c_size_t
     lib.gsr_lbs_offset_mlp_backward.argtypes = [C.c_int, fp, fp, fp, fp, C.POINTER(fp), C.POINTER(fp), vp]
     lib.gsr_lbs_offset_mlp_backward.restype = C.c_int
+    # bone-count variants: the same arguments after a leading nb (24 or 55)
+    for name in ("gsr_lbs_offset_mlp_packed_floats", "gsr_lbs_offset_mlp_pack", "gsr_lbs_offset_mlp_forward",
+                 "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward"):
+        getattr(lib, name + "_nb").argtypes = [C.c_int] + getattr(lib, name).argtypes
+        getattr(lib, name + "_nb").restype = getattr(lib, name).restype
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

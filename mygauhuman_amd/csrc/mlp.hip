@@ -2,7 +2,7 @@
 // motion_offset_flag is set: gaussian_renderer/__init__.py:100-106) as ONE kernel on the matrix cores, forward pass.
 //
 //   emb[63]  = (x, sin(2^o x), cos(2^o x), o = 0..9)                                   (get_embedder(10), :34-77)
-//   h1 = relu(W0 emb + b0)   h2 = relu(W1 h1 + b1)   h3 = relu(W2 h2 + b2)   h4 = relu(W3 [emb; h3] + b3)   out[24] = Wfc h4 + bfc
+//   h1 = relu(W0 emb + b0)   h2 = relu(W1 h1 + b1)   h3 = relu(W2 h2 + b2)   h4 = relu(W3 [emb; h3] + b3)   out[nb] = Wfc h4 + bfc, nb = 24 | 55
 // In plain torch this is five skinny fp32 GEMMs over 200k points plus a dozen elementwise kernels on 100-MB activations: 1.4 ms of a
 // forward whose rasterizer takes 0.25.  Here the activations never leave the registers:
 //   * a wave owns 32 points; an activation tile lives as the C/D fragment of v_mfma_f32_32x32x2_f32 -- column (point) on the lane,
@@ -30,36 +30,40 @@ constexpr int MLP_WG = 512;            // threads per workgroup of the forward /
 constexpr int MLP_WG_POINTS = MLP_WG / 2;
 
 constexpr int MLP_LAYERS = 5;
-constexpr int MLP_E = 63, MLP_W = 128, MLP_OUT = 24;
+constexpr int MLP_E = 63, MLP_W = 128;
+// The output layer (bw_fc) is NTO tiles of 32 rows, a compile-time parameter of every kernel: NTO = 1 for SMPL's 24 bones, 2 for
+// SMPL-X's 55 (rows >= the bone count pack as zero).  A packed buffer holds ONE bone count: the two layouts are not interchangeable.
+__host__ __device__ constexpr int mlp_bones(int nto) { return nto == 1 ? 24 : 55; }
 // per layer: input tiles of 32 features, output tiles of 32 features
 __host__ __device__ constexpr int mlp_tin(int l) { return l == 0 ? 2 : (l == 3 ? 6 : 4); }
-__host__ __device__ constexpr int mlp_tout(int l) { return l == 4 ? 1 : 4; }
+__host__ __device__ constexpr int mlp_tout(int l, int nto) { return l == 4 ? nto : 4; }
 // packed A fragments of a layer: [input tile][accumulator register 0..15][lane 0..63][output tile]
-__host__ __device__ constexpr int mlp_packed_floats(int l) { return mlp_tin(l) * 16 * 64 * mlp_tout(l); }
-__host__ __device__ constexpr int mlp_packed_offset(int l) {
+__host__ __device__ constexpr int mlp_packed_floats(int l, int nto) { return mlp_tin(l) * 16 * 64 * mlp_tout(l, nto); }
+__host__ __device__ constexpr int mlp_packed_offset(int l, int nto) {
   int o = 0;
-  for (int k = 0; k < l; k++) o += mlp_packed_floats(k);
+  for (int k = 0; k < l; k++) o += mlp_packed_floats(k, nto);
   return o;
 }
-constexpr int MLP_PACKED_W = mlp_packed_offset(MLP_LAYERS);     // floats of all packed weights
-constexpr int MLP_PACKED_B = 4 * MLP_W + 32;                      // biases, the last layer padded to 32
-constexpr int MLP_PACKED = MLP_PACKED_W + MLP_PACKED_B;
-constexpr int MLP_LDS_FLOATS = mlp_packed_floats(3);              // the largest layer: 6 x 16 x 64 x 4 floats = 96 KB
+__host__ __device__ constexpr int mlp_packed_w(int nto) { return mlp_packed_offset(MLP_LAYERS, nto); }   // floats of all packed weights
+__host__ __device__ constexpr int mlp_packed_b(int nto) { return 4 * MLP_W + 32 * nto; }   // biases, the last layer padded to 32 nto
+__host__ __device__ constexpr int mlp_packed(int nto) { return mlp_packed_w(nto) + mlp_packed_b(nto); }
+constexpr int MLP_LDS_FLOATS = mlp_packed_floats(3, 1);           // the largest layer: 6 x 16 x 64 x 4 floats = 96 KB (either nto)
+static_assert(mlp_packed_floats(4, 2) <= MLP_LDS_FLOATS, "the output layer fits the staging buffer");
 // backward (dh = W^T dZ) fragments, steps 0..3 = layers fc, 3, 2, 1: [o tile of dZ][register][lane][k tile of dh]; layer 0 has no
 // input gradient (the positions are detached: gaussian_renderer/__init__.py:104) and layer 3 only its h part
-__host__ __device__ constexpr int mlp_bwd_tin(int s) { return s == 0 ? 1 : 4; }
-__host__ __device__ constexpr int mlp_bwd_floats(int s) { return mlp_bwd_tin(s) * 16 * 64 * 4; }
-__host__ __device__ constexpr int mlp_bwd_offset(int s) {
-  int o = MLP_PACKED;
-  for (int k = 0; k < s; k++) o += mlp_bwd_floats(k);
+__host__ __device__ constexpr int mlp_bwd_tin(int s, int nto) { return s == 0 ? nto : 4; }
+__host__ __device__ constexpr int mlp_bwd_floats(int s, int nto) { return mlp_bwd_tin(s, nto) * 16 * 64 * 4; }
+__host__ __device__ constexpr int mlp_bwd_offset(int s, int nto) {
+  int o = mlp_packed(nto);
+  for (int k = 0; k < s; k++) o += mlp_bwd_floats(k, nto);
   return o;
 }
-constexpr int MLP_PACKED_ALL = mlp_bwd_offset(4);
+__host__ __device__ constexpr int mlp_packed_all(int nto) { return mlp_bwd_offset(4, nto); }
 // bf16 fragments ("bf16x3": every weight as two bf16 terms, hi + lo), the same float counts and offsets as the f32 fragments:
 // 16-byte units [input tile][k-step 0..1][output tile][hi | lo][lane], eight bf16 each
-constexpr int MLP_PACKED_FWD16 = MLP_PACKED_ALL;                                  // bf16 forward fragments
-constexpr int MLP_PACKED_BWD16 = MLP_PACKED_FWD16 + MLP_PACKED_W;                 // bf16 backward fragments (steps fc, 3, 2, 1)
-constexpr int MLP_PACKED_TOTAL = MLP_PACKED_BWD16 + (MLP_PACKED_ALL - MLP_PACKED);
+__host__ __device__ constexpr int mlp_packed_fwd16(int nto) { return mlp_packed_all(nto); }   // bf16 forward fragments
+__host__ __device__ constexpr int mlp_packed_bwd16(int nto) { return mlp_packed_fwd16(nto) + mlp_packed_w(nto); }   // bf16 backward
+__host__ __device__ constexpr int mlp_packed_total(int nto) { return mlp_packed_bwd16(nto) + (mlp_packed_all(nto) - mlp_packed(nto)); }
 
 __host__ __device__ constexpr int mlp_row_of_reg(int i) { return (i & 3) + 8 * (i >> 2); }
 
@@ -74,23 +78,26 @@ struct MlpWeights {   // the reference module's tensors (Conv1d weight [out][in]
 };
 
 // one thread per packed float
+template <int NTO>
 __global__ __launch_bounds__(256) void mlp_pack_kernel(const MlpWeights src, float *packed) {
+  constexpr int NB = mlp_bones(NTO), PACKED = mlp_packed(NTO), PACKED_W = mlp_packed_w(NTO), PACKED_ALL = mlp_packed_all(NTO),
+                BWD16 = mlp_packed_bwd16(NTO);
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= MLP_PACKED_TOTAL) return;
-  if (e >= MLP_PACKED_BWD16) {   // backward fragments in bf16: W_l[o = the k of the step][column of input feature kf]
-    const int r0 = e - MLP_PACKED_BWD16 + MLP_PACKED;
-    int st = 0, base = MLP_PACKED;
+  if (e >= mlp_packed_total(NTO)) return;
+  if (e >= BWD16) {   // backward fragments in bf16: W_l[o = the k of the step][column of input feature kf]
+    const int r0 = e - BWD16 + PACKED;
+    int st = 0, base = PACKED;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      if (r0 >= mlp_bwd_offset(k)) {
+      if (r0 >= mlp_bwd_offset(k, NTO)) {
         st = k;
-        base = mlp_bwd_offset(k);
+        base = mlp_bwd_offset(k, NTO);
       }
     }
     const int l = 4 - st, r = r0 - base, unit = r / 4, sub = r % 4;
     const int lane = unit % 64, hl = (unit / 64) % 2, t_out = (unit / 128) % 4, ks = (unit / 512) % 2, t_in = unit / 1024;
     const int kf = 32 * t_out + (lane & 31), ncols = l == 3 ? MLP_E + MLP_W : MLP_W, col = l == 3 ? MLP_E + kf : kf;
-    const int nrows = l == 4 ? MLP_OUT : MLP_W;
+    const int nrows = l == 4 ? NB : MLP_W;
     uint32_t word = 0;
     for (int q = 0; q < 2; q++) {
       const int j = 2 * sub + q;
@@ -102,19 +109,19 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const MlpWeights src, flo
     reinterpret_cast<uint32_t *>(packed)[e] = word;
     return;
   }
-  if (e >= MLP_PACKED_ALL) {   // two bf16 elements (2 sub, 2 sub + 1) of a 16-byte fragment unit
-    const int r0 = e - MLP_PACKED_ALL;
+  if (e >= PACKED_ALL) {   // two bf16 elements (2 sub, 2 sub + 1) of a 16-byte fragment unit
+    const int r0 = e - PACKED_ALL;
     int l = 0, base = 0;
 #pragma unroll
     for (int k = 0; k < MLP_LAYERS; k++) {
-      if (r0 >= mlp_packed_offset(k)) {
+      if (r0 >= mlp_packed_offset(k, NTO)) {
         l = k;
-        base = mlp_packed_offset(k);
+        base = mlp_packed_offset(k, NTO);
       }
     }
-    const int nto = mlp_tout(l), r = r0 - base, unit = r / 4, sub = r % 4;
+    const int nto = mlp_tout(l, NTO), r = r0 - base, unit = r / 4, sub = r % 4;
     const int lane = unit % 64, hl = (unit / 64) % 2, t_out = (unit / 128) % nto, ks = (unit / 128 / nto) % 2, t_in = unit / 128 / nto / 2;
-    const int o = 32 * t_out + (lane & 31), nrows = l == 4 ? MLP_OUT : MLP_W;
+    const int o = 32 * t_out + (lane & 31), nrows = l == 4 ? NB : MLP_W;
     uint32_t word = 0;
     for (int q = 0; q < 2; q++) {
       const int j = 2 * sub + q;
@@ -134,36 +141,36 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const MlpWeights src, flo
     reinterpret_cast<uint32_t *>(packed)[e] = word;
     return;
   }
-  if (e >= MLP_PACKED) {   // backward fragments: W_l[o][column of input feature k]
-    int st = 0, base = MLP_PACKED;
+  if (e >= PACKED) {   // backward fragments: W_l[o][column of input feature k]
+    int st = 0, base = PACKED;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      if (e >= mlp_bwd_offset(k)) {
+      if (e >= mlp_bwd_offset(k, NTO)) {
         st = k;
-        base = mlp_bwd_offset(k);
+        base = mlp_bwd_offset(k, NTO);
       }
     }
     const int l = 4 - st, r = e - base;
     const int t_out = r % 4, lane = (r / 4) % 64, i = (r / 4 / 64) % 16, t_in = r / 4 / 64 / 16;
     const int o = 32 * t_in + mlp_row_of_reg(i) + 4 * (lane >> 5), kf = 32 * t_out + (lane & 31);
-    const int ncols = l == 3 ? MLP_E + MLP_W : MLP_W, col = l == 3 ? MLP_E + kf : kf, nrows = l == 4 ? MLP_OUT : MLP_W;
+    const int ncols = l == 3 ? MLP_E + MLP_W : MLP_W, col = l == 3 ? MLP_E + kf : kf, nrows = l == 4 ? NB : MLP_W;
     packed[e] = o < nrows ? src.w[l][(size_t)o * ncols + col] : 0.f;
     return;
   }
-  if (e >= MLP_PACKED_W) {
-    const int k = e - MLP_PACKED_W, l = k / MLP_W, o = k % MLP_W;
-    packed[e] = l < 4 ? src.b[l][o] : (o < MLP_OUT ? src.b[4][o] : 0.f);
+  if (e >= PACKED_W) {
+    const int k = e - PACKED_W, l = k / MLP_W, o = k % MLP_W;
+    packed[e] = l < 4 ? src.b[l][o] : (o < NB ? src.b[4][o] : 0.f);
     return;
   }
   int l = 0, base = 0;
 #pragma unroll
   for (int k = 0; k < MLP_LAYERS; k++) {
-    if (e >= mlp_packed_offset(k)) {
+    if (e >= mlp_packed_offset(k, NTO)) {
       l = k;
-      base = mlp_packed_offset(k);
+      base = mlp_packed_offset(k, NTO);
     }
   }
-  const int nto = mlp_tout(l), r = e - base;
+  const int nto = mlp_tout(l, NTO), r = e - base;
   const int t_out = r % nto, lane = (r / nto) % 64, i = (r / nto / 64) % 16, t_in = r / nto / 64 / 16;
   const int o = 32 * t_out + (lane & 31);
   const int k = 32 * t_in + mlp_row_of_reg(i) + 4 * (lane >> 5);
@@ -176,7 +183,7 @@ __global__ __launch_bounds__(256) void mlp_pack_kernel(const MlpWeights src, flo
   } else {
     ncols = MLP_W, col = k;
   }
-  if (l == 4) nrows = MLP_OUT;
+  if (l == 4) nrows = NB;
   packed[e] = (col >= 0 && o < nrows) ? src.w[l][(size_t)o * ncols + col] : 0.f;
 }
 
@@ -214,7 +221,7 @@ __device__ __forceinline__ void mlp_embed_tiles(f32x16 (&emb)[2], int half, floa
 // out[to] += A-fragments(s_w) x in[ti]: NTI input tiles (32 features each) -> NTO output tiles, 16 k-steps per input tile
 template <int NTI, int NTO>
 __device__ __forceinline__ void mlp_mm(const float *s_w, const f32x16 (&in)[NTI], f32x16 (&out)[NTO], uint32_t lane) {
-  static_assert(NTO == 4 || NTO == 1, "four output tiles (one 16-byte fragment read per k-step) or one");
+  static_assert(NTO == 4 || NTO == 2 || NTO == 1, "four output tiles (one 16-byte fragment read per k-step), two or one");
 #pragma unroll
   for (int ti = 0; ti < NTI; ti++) {
 #pragma unroll
@@ -225,6 +232,10 @@ __device__ __forceinline__ void mlp_mm(const float *s_w, const f32x16 (&in)[NTI]
         out[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in[ti][i], out[1], 0, 0, 0);
         out[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in[ti][i], out[2], 0, 0, 0);
         out[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in[ti][i], out[3], 0, 0, 0);
+      } else if constexpr (NTO == 2) {
+        const float2 a = *reinterpret_cast<const float2 *>(&s_w[((ti * 16 + i) * 64 + lane) * 2]);
+        out[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in[ti][i], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in[ti][i], out[1], 0, 0, 0);
       } else {
         const float a = s_w[(ti * 16 + i) * 64 + lane];
         out[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, in[ti][i], out[0], 0, 0, 0);
@@ -233,10 +244,10 @@ __device__ __forceinline__ void mlp_mm(const float *s_w, const f32x16 (&in)[NTI]
   }
 }
 
-template <int L, int NIN>
-__device__ __forceinline__ void mlp_layer(const float *s_w, const float *bias, const f32x16 (&in)[NIN], f32x16 (&out)[mlp_tout(L)],
-                                          uint32_t lane) {
-  constexpr int NTO = mlp_tout(L);
+template <int L, int NIN, int NTO_FC = 1>   // NTO_FC: the output layer's tiles (mlp_tout)
+__device__ __forceinline__ void mlp_layer(const float *s_w, const float *bias, const f32x16 (&in)[NIN],
+                                          f32x16 (&out)[mlp_tout(L, NTO_FC)], uint32_t lane) {
+  constexpr int NTO = mlp_tout(L, NTO_FC);
   static_assert(NIN == mlp_tin(L), "input tiles of the layer");
   const uint32_t half = lane >> 5;
 #pragma unroll
@@ -288,14 +299,31 @@ __device__ __forceinline__ void mlp_commit(const f32x16 (&pre)[NP], float *s_w) 
                                                      pre[j / 4][4 * (j % 4) + 3]);
 }
 
-template <int L>
+template <int L, int NTO = 1>
 __device__ __forceinline__ void mlp_stage(const float *packed, float *s_w) {
-  mlp_stage_block<mlp_packed_offset(L), mlp_packed_floats(L)>(packed, s_w);
+  mlp_stage_block<mlp_packed_offset(L, NTO), mlp_packed_floats(L, NTO)>(packed, s_w);
 }
 
+// the output tiles -> out [P][NB] (rows >= NB: padding)
+template <int NTO>
+__device__ __forceinline__ void mlp_store_out(const f32x16 (&o)[NTO], int p, int P, uint32_t half, float *out) {
+  constexpr int NB = mlp_bones(NTO);
+  if (p < P) {
+#pragma unroll
+    for (int t = 0; t < NTO; t++) {
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const int row = 32 * t + mlp_row_of_reg(i) + 4 * (int)half;
+        if (row < NB) out[(size_t)p * NB + row] = o[t][i];
+      }
+    }
+  }
+}
+
+template <int NTO>
 __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_forward_kernel(int P, const float *xyz, const float *packed,
                                                                                                    float *out) {
-  extern __shared__ __attribute__((aligned(16))) float s_mlp[];   // MLP_LDS_FLOATS weights + MLP_PACKED_B biases
+  extern __shared__ __attribute__((aligned(16))) float s_mlp[];   // MLP_LDS_FLOATS weights + mlp_packed_b(NTO) biases
   float *s_w = s_mlp, *s_b = s_mlp + MLP_LDS_FLOATS;
   const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, half = lane >> 5;
   const int p = (int)(blockIdx.x * (uint32_t)MLP_WG_POINTS + wave * 32u + (lane & 31u));
@@ -305,7 +333,7 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     y = xyz[(size_t)p * 3 + 1];
     z = xyz[(size_t)p * 3 + 2];
   }
-  for (int q = threadIdx.x; q < MLP_PACKED_B; q += MLP_WG) s_b[q] = packed[MLP_PACKED_W + q];
+  for (int q = threadIdx.x; q < mlp_packed_b(NTO); q += MLP_WG) s_b[q] = packed[mlp_packed_w(NTO) + q];
   mlp_stage<0>(packed, s_w);
   f32x16 emb[2];
   mlp_embed_tiles<false>(emb, (int)half, x, y, z);
@@ -332,17 +360,11 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   }
   mlp_relu(b);
   __syncthreads();
-  mlp_stage<4>(packed, s_w);
+  mlp_stage<4, NTO>(packed, s_w);
   __syncthreads();
-  f32x16 o[1];
-  mlp_layer<4, 4>(s_w, s_b + 4 * MLP_W, b, o, lane);
-  if (p < P) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int row = mlp_row_of_reg(i) + 4 * (int)half;
-      if (row < MLP_OUT) out[(size_t)p * MLP_OUT + row] = o[0][i];
-    }
-  }
+  f32x16 o[NTO];
+  mlp_layer<4, 4, NTO>(s_w, s_b + 4 * MLP_W, b, o, lane);
+  mlp_store_out<NTO>(o, p, P, half, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -394,10 +416,10 @@ __device__ __forceinline__ void mlp_mm_bf16(const uint4 *s_w, const uint4 (&fh)[
   }
 }
 
-template <int L, int NIN>
+template <int L, int NIN, int NTO_FC = 1>
 __device__ __forceinline__ void mlp_layer_bf16(const uint4 *s_w, const float *bias, const uint4 (&fh)[NIN][2], const uint4 (&fl)[NIN][2],
-                                               f32x16 (&out)[mlp_tout(L)], uint32_t lane) {
-  constexpr int NTO = mlp_tout(L);
+                                               f32x16 (&out)[mlp_tout(L, NTO_FC)], uint32_t lane) {
+  constexpr int NTO = mlp_tout(L, NTO_FC);
   static_assert(NIN == mlp_tin(L), "input tiles of the layer");
   const uint32_t half = lane >> 5;
 #pragma unroll
@@ -408,11 +430,12 @@ __device__ __forceinline__ void mlp_layer_bf16(const uint4 *s_w, const float *bi
   mlp_mm_bf16<NIN, NTO>(s_w, fh, fl, out, lane);
 }
 
-template <int L>
+template <int L, int NTO>
 __device__ __forceinline__ void mlp_stage_bf16(const float *packed, float *s_w) {
-  mlp_stage_block<MLP_PACKED_ALL + mlp_packed_offset(L), mlp_packed_floats(L)>(packed, s_w);
+  mlp_stage_block<mlp_packed_fwd16(NTO) + mlp_packed_offset(L, NTO), mlp_packed_floats(L, NTO)>(packed, s_w);
 }
 
+template <int NTO>
 __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_forward_bf16x3_kernel(int P, const float *xyz,
                                                                                                           const float *packed, float *out) {
   extern __shared__ __attribute__((aligned(16))) float s_mlp[];
@@ -426,8 +449,8 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     y = xyz[(size_t)p * 3 + 1];
     z = xyz[(size_t)p * 3 + 2];
   }
-  for (int q = threadIdx.x; q < MLP_PACKED_B; q += MLP_WG) s_b[q] = packed[MLP_PACKED_W + q];
-  mlp_stage_bf16<0>(packed, s_w);
+  for (int q = threadIdx.x; q < mlp_packed_b(NTO); q += MLP_WG) s_b[q] = packed[mlp_packed_w(NTO) + q];
+  mlp_stage_bf16<0, NTO>(packed, s_w);
   f32x16 pre[MLP_PRE];
   uint4 eh[2][2], el[2][2];
   {
@@ -438,28 +461,28 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   __syncthreads();
   f32x16 a[4];
   uint4 fh[4][2], fl[4][2];
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(1), mlp_packed_floats(1)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(1, NTO), mlp_packed_floats(1, NTO)>(packed, pre);
   mlp_layer_bf16<0, 2>(s_f, s_b, eh, el, a, lane);
   mlp_relu(a);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(1)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(1, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(2), mlp_packed_floats(2)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(2, NTO), mlp_packed_floats(2, NTO)>(packed, pre);
   mlp_layer_bf16<1, 4>(s_f, s_b + MLP_W, fh, fl, a, lane);
   mlp_relu(a);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(2)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(2, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(3), mlp_packed_floats(3)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(3, NTO), mlp_packed_floats(3, NTO)>(packed, pre);
   mlp_layer_bf16<2, 4>(s_f, s_b + 2 * MLP_W, fh, fl, a, lane);
   mlp_relu(a);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(3)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(3, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(4), mlp_packed_floats(4)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(4, NTO), mlp_packed_floats(4, NTO)>(packed, pre);
   {
     uint4 ch[6][2], cl[6][2];
 #pragma unroll
@@ -475,17 +498,11 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   mlp_relu(a);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(4)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(4, NTO)>(pre, s_w);
   __syncthreads();
-  f32x16 o[1];
-  mlp_layer_bf16<4, 4>(s_f, s_b + 4 * MLP_W, fh, fl, o, lane);
-  if (p < P) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int row = mlp_row_of_reg(i) + 4 * (int)half;
-      if (row < MLP_OUT) out[(size_t)p * MLP_OUT + row] = o[0][i];
-    }
-  }
+  f32x16 o[NTO];
+  mlp_layer_bf16<4, 4, NTO>(s_f, s_b + 4 * MLP_W, fh, fl, o, lane);
+  mlp_store_out<NTO>(o, p, P, half, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -497,9 +514,25 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 //   wgrad : dW_l[o][k] = sum_p dZ_l[o][p] X_{l-1}[k][p] -- both operands are now contiguous along p, which is the contraction index
 //           of this product: tiles of 32 points go through LDS (row stride 33: conflict-free operand reads) into A[i = o][kk = p]
 //           and B[kk = p][j = k] fragments; a workgroup owns a chunk of points of ONE layer and adds its partial dW / db with atomics.
-// Workspace rows (each Pp = P rounded up to a workgroup's 256 points, floats): emb 64 | h1 128 | h2 128 | h3 128 | h4 128 | dZ0..dZ3 4 x 128 | dOut^T 32.
+// Workspace rows (each Pp = P rounded up to a workgroup's 256 points, floats): emb 64 | h1 128 | h2 128 | h3 128 | h4 128 | dZ0..dZ3 4 x 128 |
+// dOut^T 32 nto.
 constexpr int MLP_WS_EMB = 0, MLP_WS_H1 = 64, MLP_WS_H4 = MLP_WS_H1 + 3 * MLP_W, MLP_WS_DZ0 = MLP_WS_H4 + MLP_W,
-              MLP_WS_DOUT = MLP_WS_DZ0 + 4 * MLP_W, MLP_WS_ROWS = MLP_WS_DOUT + 32;
+              MLP_WS_DOUT = MLP_WS_DZ0 + 4 * MLP_W;
+__host__ __device__ constexpr int mlp_ws_rows(int nto) { return MLP_WS_DOUT + 32 * nto; }
+
+// dL/dout [P][NB] -> NTO tiles (rows >= NB and points >= P: zero)
+template <int NTO>
+__device__ __forceinline__ void mlp_load_dout(f32x16 (&d)[NTO], const float *dout, int p, int P, uint32_t half) {
+  constexpr int NB = mlp_bones(NTO);
+#pragma unroll
+  for (int t = 0; t < NTO; t++) {
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      const int row = 32 * t + mlp_row_of_reg(i) + 4 * (int)half;
+      d[t][i] = (row < NB && p < P) ? dout[(size_t)p * NB + row] : 0.f;
+    }
+  }
+}
 
 template <int NT>
 __device__ __forceinline__ void mlp_store_tiles(float *ws, size_t Pp, int row0, const f32x16 (&t)[NT], int pcol, uint32_t half) {
@@ -536,6 +569,7 @@ __device__ __forceinline__ void mlp_zero(f32x16 (&t)[4]) {
   }
 }
 
+template <int NTO>
 __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_backward_chain_kernel(
     int P, int Pp_, const float *xyz, const float *packed, const float *dout, float *ws) {
   extern __shared__ __attribute__((aligned(16))) float s_mlp[];
@@ -549,7 +583,7 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     y = xyz[(size_t)p * 3 + 1];
     z = xyz[(size_t)p * 3 + 2];
   }
-  for (int q = threadIdx.x; q < MLP_PACKED_B; q += MLP_WG) s_b[q] = packed[MLP_PACKED_W + q];
+  for (int q = threadIdx.x; q < mlp_packed_b(NTO); q += MLP_WG) s_b[q] = packed[mlp_packed_w(NTO) + q];
   mlp_stage<0>(packed, s_w);
   f32x16 emb[2];
   mlp_embed_tiles<false>(emb, (int)half, x, y, z);
@@ -582,37 +616,33 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   }
   mlp_relu_mask(b, m4);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_H4, b, p, half);
-  // ---- backward: dOut (rows = the 24 outputs, padded to 32) -> dh4 -> dZ3 -> dh3 -> dZ2 -> dh2 -> dZ1 -> dh1 -> dZ0
-  f32x16 d[1];
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    const int row = mlp_row_of_reg(i) + 4 * (int)half;
-    d[0][i] = (row < MLP_OUT && p < P) ? dout[(size_t)p * MLP_OUT + row] : 0.f;
-  }
-  mlp_store_tiles<1>(ws, Pp, MLP_WS_DOUT, d, p, half);
+  // ---- backward: dOut (rows = the bones, padded to 32 NTO) -> dh4 -> dZ3 -> dh3 -> dZ2 -> dh2 -> dZ1 -> dh1 -> dZ0
+  f32x16 d[NTO];
+  mlp_load_dout<NTO>(d, dout, p, P, half);
+  mlp_store_tiles<NTO>(ws, Pp, MLP_WS_DOUT, d, p, half);
   __syncthreads();
-  mlp_stage_block<mlp_bwd_offset(0), mlp_bwd_floats(0)>(packed, s_w);
+  mlp_stage_block<mlp_bwd_offset(0, NTO), mlp_bwd_floats(0, NTO)>(packed, s_w);
   __syncthreads();
   mlp_zero(a);
-  mlp_mm<1, 4>(s_w, d, a, lane);
+  mlp_mm<NTO, 4>(s_w, d, a, lane);
   mlp_apply_mask(a, m4);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + 3 * MLP_W, a, p, half);
   __syncthreads();
-  mlp_stage_block<mlp_bwd_offset(1), mlp_bwd_floats(1)>(packed, s_w);
+  mlp_stage_block<mlp_bwd_offset(1, NTO), mlp_bwd_floats(1, NTO)>(packed, s_w);
   __syncthreads();
   mlp_zero(b);
   mlp_mm<4, 4>(s_w, a, b, lane);
   mlp_apply_mask(b, m3);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + 2 * MLP_W, b, p, half);
   __syncthreads();
-  mlp_stage_block<mlp_bwd_offset(2), mlp_bwd_floats(2)>(packed, s_w);
+  mlp_stage_block<mlp_bwd_offset(2, NTO), mlp_bwd_floats(2, NTO)>(packed, s_w);
   __syncthreads();
   mlp_zero(a);
   mlp_mm<4, 4>(s_w, b, a, lane);
   mlp_apply_mask(a, m2);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + MLP_W, a, p, half);
   __syncthreads();
-  mlp_stage_block<mlp_bwd_offset(3), mlp_bwd_floats(3)>(packed, s_w);
+  mlp_stage_block<mlp_bwd_offset(3, NTO), mlp_bwd_floats(3, NTO)>(packed, s_w);
   __syncthreads();
   mlp_zero(b);
   mlp_mm<4, 4>(s_w, a, b, lane);
@@ -621,11 +651,7 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 }
 
 // the chain kernel on the bf16 instruction (both operands split in two bf16 terms, see mlp_forward_bf16x3_kernel): what the module runs
-template <int ST>
-__device__ __forceinline__ void mlp_stage_bwd16(const float *packed, float *s_w) {
-  mlp_stage_block<MLP_PACKED_BWD16 + (mlp_bwd_offset(ST) - MLP_PACKED), mlp_bwd_floats(ST)>(packed, s_w);
-}
-
+template <int NTO>
 __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) void mlp_backward_chain_bf16x3_kernel(
     int P, int Pp_, const float *xyz, const float *packed, const float *dout, float *ws) {
   extern __shared__ __attribute__((aligned(16))) float s_mlp[];
@@ -640,8 +666,8 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     y = xyz[(size_t)p * 3 + 1];
     z = xyz[(size_t)p * 3 + 2];
   }
-  for (int q = threadIdx.x; q < MLP_PACKED_B; q += MLP_WG) s_b[q] = packed[MLP_PACKED_W + q];
-  mlp_stage_bf16<0>(packed, s_w);
+  for (int q = threadIdx.x; q < mlp_packed_b(NTO); q += MLP_WG) s_b[q] = packed[mlp_packed_w(NTO) + q];
+  mlp_stage_bf16<0, NTO>(packed, s_w);
   f32x16 pre[2];   // (two vectors = 64 KB per workgroup in flight: a third spills in this kernel; layer 3's last 32 KB are staged directly)
   uint4 eh[2][2], el[2][2];
   {
@@ -655,32 +681,32 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   f32x16 a[4];
   uint4 fh[4][2], fl[4][2];
   uint32_t m1[2], m2[2], m3[2], m4[2];
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(1), mlp_packed_floats(1)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(1, NTO), mlp_packed_floats(1, NTO)>(packed, pre);
   mlp_layer_bf16<0, 2>(s_f, s_b, eh, el, a, lane);
   mlp_relu_mask(a, m1);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_H1, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(1)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(1, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(2), mlp_packed_floats(2)>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(2, NTO), mlp_packed_floats(2, NTO)>(packed, pre);
   mlp_layer_bf16<1, 4>(s_f, s_b + MLP_W, fh, fl, a, lane);
   mlp_relu_mask(a, m2);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_H1 + MLP_W, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_packed_floats(2)>(pre, s_w);
+  mlp_commit<mlp_packed_floats(2, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_FWD16 + mlp_packed_offset(3), 16384>(packed, pre);
+  mlp_prefetch<mlp_packed_fwd16(NTO) + mlp_packed_offset(3, NTO), 16384>(packed, pre);
   mlp_layer_bf16<2, 4>(s_f, s_b + 2 * MLP_W, fh, fl, a, lane);
   mlp_relu_mask(a, m3);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_H1 + 2 * MLP_W, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
   mlp_commit<16384>(pre, s_w);
-  mlp_stage_block<MLP_PACKED_FWD16 + mlp_packed_offset(3) + 16384, mlp_packed_floats(3) - 16384>(packed, s_w + 16384);
+  mlp_stage_block<mlp_packed_fwd16(NTO) + mlp_packed_offset(3, NTO) + 16384, mlp_packed_floats(3, NTO) - 16384>(packed, s_w + 16384);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_BWD16 + (mlp_bwd_offset(0) - MLP_PACKED), mlp_bwd_floats(0)>(packed, pre);
+  mlp_prefetch<mlp_packed_bwd16(NTO) + (mlp_bwd_offset(0, NTO) - mlp_packed(NTO)), mlp_bwd_floats(0, NTO)>(packed, pre);
   {
     uint4 ch[6][2], cl[6][2];
 #pragma unroll
@@ -696,46 +722,42 @@ __global__ __launch_bounds__(MLP_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   mlp_relu_mask(a, m4);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_H4, a, p, half);
   // ---- backward: dOut -> dh4 -> dZ3 -> dh3 -> dZ2 -> dh2 -> dZ1 -> dh1 -> dZ0
-  uint4 dh[1][2], dl[1][2];
+  uint4 dh[NTO][2], dl[NTO][2];
   {
-    f32x16 d[1];
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const int row = mlp_row_of_reg(i) + 4 * (int)half;
-      d[0][i] = (row < MLP_OUT && p < P) ? dout[(size_t)p * MLP_OUT + row] : 0.f;
-    }
-    mlp_store_tiles<1>(ws, Pp, MLP_WS_DOUT, d, p, half);
-    mlp_split_tiles<1>(d, dh, dl);
+    f32x16 d[NTO];
+    mlp_load_dout<NTO>(d, dout, p, P, half);
+    mlp_store_tiles<NTO>(ws, Pp, MLP_WS_DOUT, d, p, half);
+    mlp_split_tiles<NTO>(d, dh, dl);
   }
   __syncthreads();
-  mlp_commit<mlp_bwd_floats(0)>(pre, s_w);
+  mlp_commit<mlp_bwd_floats(0, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_BWD16 + (mlp_bwd_offset(1) - MLP_PACKED), mlp_bwd_floats(1)>(packed, pre);
+  mlp_prefetch<mlp_packed_bwd16(NTO) + (mlp_bwd_offset(1, NTO) - mlp_packed(NTO)), mlp_bwd_floats(1, NTO)>(packed, pre);
   mlp_zero(a);
-  mlp_mm_bf16<1, 4>(s_f, dh, dl, a, lane);
+  mlp_mm_bf16<NTO, 4>(s_f, dh, dl, a, lane);
   mlp_apply_mask(a, m4);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + 3 * MLP_W, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_bwd_floats(1)>(pre, s_w);
+  mlp_commit<mlp_bwd_floats(1, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_BWD16 + (mlp_bwd_offset(2) - MLP_PACKED), mlp_bwd_floats(2)>(packed, pre);
+  mlp_prefetch<mlp_packed_bwd16(NTO) + (mlp_bwd_offset(2, NTO) - mlp_packed(NTO)), mlp_bwd_floats(2, NTO)>(packed, pre);
   mlp_zero(a);
   mlp_mm_bf16<4, 4>(s_f, fh, fl, a, lane);
   mlp_apply_mask(a, m3);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + 2 * MLP_W, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_bwd_floats(2)>(pre, s_w);
+  mlp_commit<mlp_bwd_floats(2, NTO)>(pre, s_w);
   __syncthreads();
-  mlp_prefetch<MLP_PACKED_BWD16 + (mlp_bwd_offset(3) - MLP_PACKED), mlp_bwd_floats(3)>(packed, pre);
+  mlp_prefetch<mlp_packed_bwd16(NTO) + (mlp_bwd_offset(3, NTO) - mlp_packed(NTO)), mlp_bwd_floats(3, NTO)>(packed, pre);
   mlp_zero(a);
   mlp_mm_bf16<4, 4>(s_f, fh, fl, a, lane);
   mlp_apply_mask(a, m2);
   mlp_store_tiles<4>(ws, Pp, MLP_WS_DZ0 + MLP_W, a, p, half);
   mlp_split_tiles<4>(a, fh, fl);
   __syncthreads();
-  mlp_commit<mlp_bwd_floats(3)>(pre, s_w);
+  mlp_commit<mlp_bwd_floats(3, NTO)>(pre, s_w);
   __syncthreads();
   mlp_zero(a);
   mlp_mm_bf16<4, 4>(s_f, fh, fl, a, lane);
@@ -759,7 +781,7 @@ constexpr int WG_STRIDE = 33;   // floats per staged row of 32 points
 
 template <int TA, int TB>
 __device__ __forceinline__ void mlp_wgrad_body(const MlpWgradLayer &L, const float *ws, size_t Pp, int p0, int p1, float *s_A, float *s_B) {
-  constexpr int NACC = TA == 4 ? TB : 1;   // TA == 4: wave w owns dZ tile w and every X tile; TA == 1 (fc): X tile w
+  constexpr int NACC = TA == 4 ? TB : TA;   // TA == 4: wave w owns dZ tile w and every X tile; TA = 1, 2 (fc): X tile w, every dZ tile
   const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, half = lane >> 5, r = lane & 31u;
   f32x16 acc[NACC];
 #pragma unroll
@@ -768,7 +790,6 @@ __device__ __forceinline__ void mlp_wgrad_body(const MlpWgradLayer &L, const flo
     for (int i = 0; i < 16; i++) acc[k][i] = 0.f;
   }
   float dbsum = 0.f;
-  const int my_ta = TA == 4 ? (int)wave : 0;
   // a stage = [rows][32 points], eight threads per row with 16 bytes each; the NEXT stage's global loads are issued before this
   // stage's MFMAs and land in LDS after them (the loads' latency used to sit exposed between two barriers)
   constexpr int NQ = ((TA + TB) * 32 * 8 + 255) / 256;   // 16-byte pieces per thread per stage
@@ -802,8 +823,8 @@ __device__ __forceinline__ void mlp_wgrad_body(const MlpWgradLayer &L, const flo
     if (pb + 32 < p1) fetch(pb + 32);
 #pragma unroll
     for (int s = 0; s < 16; s++) {
-      const float af = s_A[(32 * my_ta + (int)r) * WG_STRIDE + 2 * s + (int)half];
       if constexpr (TA == 4) {
+        const float af = s_A[(32 * (int)wave + (int)r) * WG_STRIDE + 2 * s + (int)half];
 #pragma unroll
         for (int tb = 0; tb < TB; tb++) {
           const float bf = s_B[(32 * tb + (int)r) * WG_STRIDE + 2 * s + (int)half];
@@ -811,7 +832,11 @@ __device__ __forceinline__ void mlp_wgrad_body(const MlpWgradLayer &L, const flo
         }
       } else {
         const float bf = s_B[(32 * (int)wave + (int)r) * WG_STRIDE + 2 * s + (int)half];
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bf, acc[0], 0, 0, 0);
+#pragma unroll
+        for (int ta = 0; ta < TA; ta++) {
+          const float af = s_A[(32 * ta + (int)r) * WG_STRIDE + 2 * s + (int)half];
+          acc[ta] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bf, acc[ta], 0, 0, 0);
+        }
       }
     }
     if ((int)threadIdx.x < TA * 32) {
@@ -825,14 +850,14 @@ __device__ __forceinline__ void mlp_wgrad_body(const MlpWgradLayer &L, const flo
   // D[i = o][j = k]: column on the lane, rows in the registers
 #pragma unroll
   for (int k = 0; k < NACC; k++) {
-    const int tb = TA == 4 ? k : (int)wave;
+    const int tb = TA == 4 ? k : (int)wave, ta = TA == 4 ? (int)wave : k;
     const int kf = 32 * tb + (int)r;
     int col = kf;
     if (L.kind == 3) col = kf < MLP_E ? kf : (kf == MLP_E ? -1 : MLP_E + (kf - 64));
     if (col >= L.ncols) col = -1;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-      const int o = 32 * my_ta + mlp_row_of_reg(i) + 4 * (int)half;
+      const int o = 32 * ta + mlp_row_of_reg(i) + 4 * (int)half;
       if (col >= 0 && o < L.nrows) atomicAdd(&L.dW[(size_t)o * L.ncols + col], acc[k][i]);
     }
   }
@@ -847,7 +872,7 @@ constexpr int WG16_STRIDE = 20;   // 32-bit words per staged row of 32 bf16
 template <int TA, int TB>
 __device__ __forceinline__ void mlp_wgrad_body_bf16(const MlpWgradLayer &L, const float *ws, size_t Pp, int p0, int p1, uint32_t *s_Ah,
                                                     uint32_t *s_Al, uint32_t *s_Bh, uint32_t *s_Bl) {
-  constexpr int NACC = TA == 4 ? TB : 1;
+  constexpr int NACC = TA == 4 ? TB : TA;
   const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, half = lane >> 5, r = lane & 31u;
   f32x16 acc[NACC];
 #pragma unroll
@@ -855,7 +880,6 @@ __device__ __forceinline__ void mlp_wgrad_body_bf16(const MlpWgradLayer &L, cons
 #pragma unroll
     for (int i = 0; i < 16; i++) acc[k][i] = 0.f;
   }
-  const int my_ta = TA == 4 ? (int)wave : 0;
   constexpr int NQ = ((TA + TB) * 32 * 8 + 255) / 256;   // 16-byte pieces per thread per stage
   constexpr int NQA = (TA * 32 * 8 + 255) / 256;          // ... of which the first NQA belong to dZ rows (row = tid / 8 + 32 j)
   float4 pre[NQ];
@@ -903,11 +927,11 @@ __device__ __forceinline__ void mlp_wgrad_body_bf16(const MlpWgradLayer &L, cons
 #pragma unroll
     for (int ks = 0; ks < 2; ks++) {
       const int fo = 8 * ks + 4 * (int)half;   // word offset of the lane's eight points inside a row
-      const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Ah + (32 * my_ta + (int)r) * WG16_STRIDE + fo));
-      const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Al + (32 * my_ta + (int)r) * WG16_STRIDE + fo));
 #pragma unroll
       for (int k = 0; k < NACC; k++) {
-        const int tb = TA == 4 ? k : (int)wave;
+        const int tb = TA == 4 ? k : (int)wave, ta = TA == 4 ? (int)wave : k;
+        const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Ah + (32 * ta + (int)r) * WG16_STRIDE + fo));
+        const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Al + (32 * ta + (int)r) * WG16_STRIDE + fo));
         const bf16x8 bh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Bh + (32 * tb + (int)r) * WG16_STRIDE + fo));
         const bf16x8 bl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_Bl + (32 * tb + (int)r) * WG16_STRIDE + fo));
         acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[k], 0, 0, 0);
@@ -919,14 +943,14 @@ __device__ __forceinline__ void mlp_wgrad_body_bf16(const MlpWgradLayer &L, cons
   }
 #pragma unroll
   for (int k = 0; k < NACC; k++) {
-    const int tb = TA == 4 ? k : (int)wave;
+    const int tb = TA == 4 ? k : (int)wave, ta = TA == 4 ? (int)wave : k;
     const int kf = 32 * tb + (int)r;
     int col = kf;
     if (L.kind == 3) col = kf < MLP_E ? kf : (kf == MLP_E ? -1 : MLP_E + (kf - 64));
     if (col >= L.ncols) col = -1;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-      const int o = 32 * my_ta + mlp_row_of_reg(i) + 4 * (int)half;
+      const int o = 32 * ta + mlp_row_of_reg(i) + 4 * (int)half;
       if (col >= 0 && o < L.nrows) atomicAdd(&L.dW[(size_t)o * L.ncols + col], acc[k][i]);
     }
   }
@@ -942,6 +966,7 @@ __device__ __forceinline__ void mlp_wgrad_body_bf16(const MlpWgradLayer &L, cons
   }
 }
 
+template <int NTO>
 __global__ __launch_bounds__(256) void mlp_wgrad_bf16x3_kernel(const MlpWgradArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t s_Ah[128 * WG16_STRIDE], s_Al[128 * WG16_STRIDE];
   __shared__ __attribute__((aligned(16))) uint32_t s_Bh[192 * WG16_STRIDE], s_Bl[192 * WG16_STRIDE];
@@ -951,11 +976,12 @@ __global__ __launch_bounds__(256) void mlp_wgrad_bf16x3_kernel(const MlpWgradArg
   switch (blockIdx.y) {
     case 0: mlp_wgrad_body_bf16<4, 2>(L, a.ws, (size_t)a.Pp, p0, p1, s_Ah, s_Al, s_Bh, s_Bl); break;
     case 3: mlp_wgrad_body_bf16<4, 6>(L, a.ws, (size_t)a.Pp, p0, p1, s_Ah, s_Al, s_Bh, s_Bl); break;
-    case 4: mlp_wgrad_body_bf16<1, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_Ah, s_Al, s_Bh, s_Bl); break;
+    case 4: mlp_wgrad_body_bf16<NTO, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_Ah, s_Al, s_Bh, s_Bl); break;
     default: mlp_wgrad_body_bf16<4, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_Ah, s_Al, s_Bh, s_Bl); break;
   }
 }
 
+template <int NTO>
 __global__ __launch_bounds__(256) void mlp_wgrad_kernel(const MlpWgradArgs a) {
   __shared__ float s_A[128 * WG_STRIDE];
   __shared__ float s_B[192 * WG_STRIDE];
@@ -965,55 +991,56 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(const MlpWgradArgs a) {
   switch (blockIdx.y) {
     case 0: mlp_wgrad_body<4, 2>(L, a.ws, (size_t)a.Pp, p0, p1, s_A, s_B); break;
     case 3: mlp_wgrad_body<4, 6>(L, a.ws, (size_t)a.Pp, p0, p1, s_A, s_B); break;
-    case 4: mlp_wgrad_body<1, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_A, s_B); break;
+    case 4: mlp_wgrad_body<NTO, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_A, s_B); break;
     default: mlp_wgrad_body<4, 4>(L, a.ws, (size_t)a.Pp, p0, p1, s_A, s_B); break;
   }
 }
 
-}  // namespace gsr
-
 static std::atomic<int> g_mlp_precision{1};   // 0: f32 MFMA, 1: bf16 MFMA with both operands split in two terms (default)
 
-extern "C" {
-
-size_t gsr_lbs_offset_mlp_packed_floats(void) { return (size_t)gsr::MLP_PACKED_TOTAL; }
-
-size_t gsr_lbs_offset_mlp_backward_workspace_floats(int P) {
-  const size_t Pp = ((size_t)(P > 0 ? P : 0) + gsr::MLP_WG_POINTS - 1) / gsr::MLP_WG_POINTS * gsr::MLP_WG_POINTS;
-  return (size_t)gsr::MLP_WS_ROWS * Pp;
+// the bone counts the kernels are compiled for -> NTO (0: not supported; the error names the value and both counts)
+static int mlp_nto(const char *who, int nb) {
+  if (nb == mlp_bones(1)) return 1;
+  if (nb == mlp_bones(2)) return 2;
+  set_error("%s: nb = %d bones is not supported (compiled bone counts: %d for SMPL, %d for SMPL-X)", who, nb, mlp_bones(1), mlp_bones(2));
+  return 0;
 }
 
-int gsr_lbs_offset_mlp_backward(int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
-                                float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream_) {
-  using namespace gsr;
+static size_t mlp_padded_points(int P) {
+  return ((size_t)(P > 0 ? P : 0) + MLP_WG_POINTS - 1) / MLP_WG_POINTS * MLP_WG_POINTS;
+}
+
+template <int NTO>
+static int mlp_backward(const char *who, int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
+                        float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream_) {
   if (P < 0 || (P > 0 && (!xyz || !packed || !dL_dout || !workspace || !dL_dweights || !dL_dbiases))) {
-    set_error("gsr_lbs_offset_mlp_backward: bad size or null pointer");
+    set_error("%s: bad size or null pointer", who);
     return GSR_EINVAL;
   }
   if (reinterpret_cast<size_t>(packed) % 16 != 0 || reinterpret_cast<size_t>(workspace) % 16 != 0) {
-    set_error("gsr_lbs_offset_mlp_backward: the packed weights and the workspace must be 16-byte aligned");
+    set_error("%s: the packed weights and the workspace must be 16-byte aligned", who);
     return GSR_EINVAL;
   }
   for (int l = 0; l < MLP_LAYERS; l++) {
     if (P > 0 && (!dL_dweights[l] || !dL_dbiases[l])) {
-      set_error("gsr_lbs_offset_mlp_backward: layer %d: null gradient array", l);
+      set_error("%s: layer %d: null gradient array", who, l);
       return GSR_EINVAL;
     }
   }
   if (P == 0) return GSR_OK;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const int Pp = (P + MLP_WG_POINTS - 1) / MLP_WG_POINTS * MLP_WG_POINTS;
-  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + MLP_PACKED_B) * sizeof(float);
-  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_backward_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+  const int Pp = (int)mlp_padded_points(P);
+  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + mlp_packed_b(NTO)) * sizeof(float);
+  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_backward_chain_kernel<NTO>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds));
-  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_backward_chain_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds));
+  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_backward_chain_bf16x3_kernel<NTO>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   if (g_mlp_precision.load() == 1)
-    hipLaunchKernelGGL(mlp_backward_chain_bf16x3_kernel, dim3((unsigned)(Pp / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, Pp, xyz, packed,
-                       dL_dout, workspace);
+    hipLaunchKernelGGL(mlp_backward_chain_bf16x3_kernel<NTO>, dim3((unsigned)(Pp / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, Pp, xyz,
+                       packed, dL_dout, workspace);
   else
-    hipLaunchKernelGGL(mlp_backward_chain_kernel, dim3((unsigned)(Pp / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, Pp, xyz, packed, dL_dout,
-                       workspace);
+    hipLaunchKernelGGL(mlp_backward_chain_kernel<NTO>, dim3((unsigned)(Pp / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, Pp, xyz, packed,
+                       dL_dout, workspace);
   GSR_HIP(hipGetLastError());
   MlpWgradArgs a;
   memset(&a, 0, sizeof(a));
@@ -1022,88 +1049,163 @@ int gsr_lbs_offset_mlp_backward(int P, const float *xyz, const float *packed, co
   for (int l = 0; l < MLP_LAYERS; l++) {
     MlpWgradLayer &L = a.L[l];
     L.a_row = l < 4 ? MLP_WS_DZ0 + l * MLP_W : MLP_WS_DOUT;
-    L.ta = l < 4 ? 4 : 1;
+    L.ta = l < 4 ? 4 : NTO;
     L.b_row0 = xrow[l];
     L.tb = mlp_tin(l);
     L.tb0 = l == 3 ? 2 : L.tb;
     L.b_row1 = MLP_WS_H1 + 2 * MLP_W;   // layer 3: h3 behind the embedding
     L.dW = dL_dweights[l], L.db = dL_dbiases[l];
-    L.nrows = l < 4 ? MLP_W : MLP_OUT;
+    L.nrows = l < 4 ? MLP_W : mlp_bones(NTO);
     L.ncols = l == 0 ? MLP_E : (l == 3 ? MLP_E + MLP_W : MLP_W);
     L.kind = l == 3 ? 3 : 0;
   }
   if (g_mlp_precision.load() == 1)
-    hipLaunchKernelGGL(mlp_wgrad_bf16x3_kernel, dim3((unsigned)((Pp + a.chunk - 1) / a.chunk), MLP_LAYERS), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mlp_wgrad_bf16x3_kernel<NTO>, dim3((unsigned)((Pp + a.chunk - 1) / a.chunk), MLP_LAYERS), dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL(mlp_wgrad_kernel, dim3((unsigned)((Pp + a.chunk - 1) / a.chunk), MLP_LAYERS), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mlp_wgrad_kernel<NTO>, dim3((unsigned)((Pp + a.chunk - 1) / a.chunk), MLP_LAYERS), dim3(256), 0, stream, a);
   return check_hip(hipGetLastError(), "mlp_wgrad_kernel", __FILE__, __LINE__);
 }
 
-
-int gsr_lbs_offset_mlp_pack(const float *const *weights, const float *const *biases, float *packed, gsr_stream_t stream_) {
-  using namespace gsr;
+template <int NTO>
+static int mlp_pack(const char *who, const float *const *weights, const float *const *biases, float *packed, gsr_stream_t stream_) {
   if (!weights || !biases || !packed) {
-    set_error("gsr_lbs_offset_mlp_pack: null argument");
+    set_error("%s: null argument", who);
     return GSR_EINVAL;
   }
   MlpWeights w;
   for (int l = 0; l < MLP_LAYERS; l++) {
     if (!weights[l] || !biases[l]) {
-      set_error("gsr_lbs_offset_mlp_pack: layer %d: null weight or bias", l);
+      set_error("%s: layer %d: null weight or bias", who, l);
       return GSR_EINVAL;
     }
     w.w[l] = weights[l];
     w.b[l] = biases[l];
   }
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  hipLaunchKernelGGL(mlp_pack_kernel, dim3((MLP_PACKED_TOTAL + 255) / 256), dim3(256), 0, stream, w, packed);
+  hipLaunchKernelGGL(mlp_pack_kernel<NTO>, dim3((mlp_packed_total(NTO) + 255) / 256), dim3(256), 0, stream, w, packed);
   return check_hip(hipGetLastError(), "mlp_pack_kernel", __FILE__, __LINE__);
 }
 
-int gsr_lbs_offset_mlp_set_precision(int mode) {
+template <int NTO>
+static int mlp_forward_bf16x3(const char *who, int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream_) {
+  if (P < 0 || (P > 0 && (!xyz || !packed || !out)) || reinterpret_cast<size_t>(packed) % 16 != 0) {
+    set_error("%s: bad size, null pointer or misaligned fragments", who);
+    return GSR_EINVAL;
+  }
+  if (P == 0) return GSR_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + mlp_packed_b(NTO)) * sizeof(float);
+  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_forward_bf16x3_kernel<NTO>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds));
+  hipLaunchKernelGGL(mlp_forward_bf16x3_kernel<NTO>, dim3((unsigned)((P + MLP_WG_POINTS - 1) / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P,
+                     xyz, packed, out);
+  return check_hip(hipGetLastError(), "mlp_forward_bf16x3_kernel", __FILE__, __LINE__);
+}
+
+template <int NTO>
+static int mlp_forward(const char *who, const char *who_bf16, int P, const float *xyz, const float *packed, float *out,
+                       gsr_stream_t stream_) {
+  if (P < 0 || (P > 0 && (!xyz || !packed || !out))) {
+    set_error("%s: bad size or null pointer", who);
+    return GSR_EINVAL;
+  }
+  if (reinterpret_cast<size_t>(packed) % 16 != 0) {
+    set_error("%s: the packed weights must be 16-byte aligned", who);
+    return GSR_EINVAL;
+  }
+  if (P == 0) return GSR_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + mlp_packed_b(NTO)) * sizeof(float);
+  static_assert(lds <= 160 * 1024, "one layer's packed weights fit the LDS of a CU");
+  // (dynamic LDS above 64 KB needs the attribute; set per call: it is per device and costs nothing)
+  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_forward_kernel<NTO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (g_mlp_precision.load() == 1) return mlp_forward_bf16x3<NTO>(who_bf16, P, xyz, packed, out, stream_);
+  hipLaunchKernelGGL(mlp_forward_kernel<NTO>, dim3((unsigned)((P + MLP_WG_POINTS - 1) / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, xyz,
+                     packed, out);
+  return check_hip(hipGetLastError(), "mlp_forward_kernel", __FILE__, __LINE__);
+}
+
+}  // namespace gsr
+
+extern "C" {
+
+// ---- the 24-bone (SMPL) entry points
+size_t gsr_lbs_offset_mlp_packed_floats(void) { return (size_t)gsr::mlp_packed_total(1); }
+
+size_t gsr_lbs_offset_mlp_backward_workspace_floats(int P) { return (size_t)gsr::mlp_ws_rows(1) * gsr::mlp_padded_points(P); }
+
+int gsr_lbs_offset_mlp_backward(int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
+                                float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream) {
+  return gsr::mlp_backward<1>("gsr_lbs_offset_mlp_backward", P, xyz, packed, dL_dout, workspace, dL_dweights, dL_dbiases, stream);
+}
+
+int gsr_lbs_offset_mlp_pack(const float *const *weights, const float *const *biases, float *packed, gsr_stream_t stream) {
+  return gsr::mlp_pack<1>("gsr_lbs_offset_mlp_pack", weights, biases, packed, stream);
+}
+
+int gsr_lbs_offset_mlp_set_precision(int mode) {   // (both bone counts)
   if (mode != 0 && mode != 1) {
     gsr::set_error("gsr_lbs_offset_mlp_set_precision: 0 (f32 matrix instruction) or 1 (bf16 instruction, operands split in two terms)");
     return GSR_EINVAL;
   }
-  g_mlp_precision.store(mode);
+  gsr::g_mlp_precision.store(mode);
   return GSR_OK;
 }
 
-int gsr_debug_lbs_offset_mlp_forward_bf16x3(int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream_) {
-  using namespace gsr;
-  if (P < 0 || (P > 0 && (!xyz || !packed || !out)) || reinterpret_cast<size_t>(packed) % 16 != 0) {
-    set_error("gsr_debug_lbs_offset_mlp_forward_bf16x3: bad size, null pointer or misaligned fragments");
-    return GSR_EINVAL;
-  }
-  if (P == 0) return GSR_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + MLP_PACKED_B) * sizeof(float);
-  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_forward_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(mlp_forward_bf16x3_kernel, dim3((unsigned)((P + MLP_WG_POINTS - 1) / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, xyz,
-                     packed, out);
-  return check_hip(hipGetLastError(), "mlp_forward_bf16x3_kernel", __FILE__, __LINE__);
+int gsr_debug_lbs_offset_mlp_forward_bf16x3(int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream) {
+  return gsr::mlp_forward_bf16x3<1>("gsr_debug_lbs_offset_mlp_forward_bf16x3", P, xyz, packed, out, stream);
 }
 
-int gsr_lbs_offset_mlp_forward(int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream_) {
-  using namespace gsr;
-  if (P < 0 || (P > 0 && (!xyz || !packed || !out))) {
-    set_error("gsr_lbs_offset_mlp_forward: bad size or null pointer");
-    return GSR_EINVAL;
+int gsr_lbs_offset_mlp_forward(int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream) {
+  return gsr::mlp_forward<1>("gsr_lbs_offset_mlp_forward", "gsr_debug_lbs_offset_mlp_forward_bf16x3", P, xyz, packed, out, stream);
+}
+
+// ---- bone-count variants: nb = 24 (the entry points above) or 55 (SMPL-X); nb is checked before anything else
+size_t gsr_lbs_offset_mlp_packed_floats_nb(int nb) {
+  const int nto = gsr::mlp_nto("gsr_lbs_offset_mlp_packed_floats_nb", nb);
+  return nto == 0 ? 0 : (size_t)(nto == 1 ? gsr::mlp_packed_total(1) : gsr::mlp_packed_total(2));
+}
+
+size_t gsr_lbs_offset_mlp_backward_workspace_floats_nb(int nb, int P) {
+  const int nto = gsr::mlp_nto("gsr_lbs_offset_mlp_backward_workspace_floats_nb", nb);
+  return nto == 0 ? 0 : (size_t)gsr::mlp_ws_rows(nto) * gsr::mlp_padded_points(P);
+}
+
+int gsr_lbs_offset_mlp_pack_nb(int nb, const float *const *weights, const float *const *biases, float *packed, gsr_stream_t stream) {
+  static const char *who = "gsr_lbs_offset_mlp_pack_nb";
+  switch (gsr::mlp_nto(who, nb)) {
+    case 1: return gsr::mlp_pack<1>(who, weights, biases, packed, stream);
+    case 2: return gsr::mlp_pack<2>(who, weights, biases, packed, stream);
+    default: return GSR_EINVAL;
   }
-  if (reinterpret_cast<size_t>(packed) % 16 != 0) {
-    set_error("gsr_lbs_offset_mlp_forward: the packed weights must be 16-byte aligned");
-    return GSR_EINVAL;
+}
+
+int gsr_lbs_offset_mlp_forward_nb(int nb, int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream) {
+  static const char *who = "gsr_lbs_offset_mlp_forward_nb", *who16 = "gsr_debug_lbs_offset_mlp_forward_bf16x3_nb";
+  switch (gsr::mlp_nto(who, nb)) {
+    case 1: return gsr::mlp_forward<1>(who, who16, P, xyz, packed, out, stream);
+    case 2: return gsr::mlp_forward<2>(who, who16, P, xyz, packed, out, stream);
+    default: return GSR_EINVAL;
   }
-  if (P == 0) return GSR_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  constexpr size_t lds = (size_t)(MLP_LDS_FLOATS + MLP_PACKED_B) * sizeof(float);
-  static_assert(lds <= 160 * 1024, "one layer's packed weights fit the LDS of a CU");
-  // (dynamic LDS above 64 KB needs the attribute; set per call: it is per device and costs nothing)
-  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (g_mlp_precision.load() == 1) return gsr_debug_lbs_offset_mlp_forward_bf16x3(P, xyz, packed, out, stream_);
-  hipLaunchKernelGGL(mlp_forward_kernel, dim3((unsigned)((P + MLP_WG_POINTS - 1) / MLP_WG_POINTS)), dim3(MLP_WG), lds, stream, P, xyz, packed,
-                     out);
-  return check_hip(hipGetLastError(), "mlp_forward_kernel", __FILE__, __LINE__);
+}
+
+int gsr_debug_lbs_offset_mlp_forward_bf16x3_nb(int nb, int P, const float *xyz, const float *packed, float *out, gsr_stream_t stream) {
+  static const char *who = "gsr_debug_lbs_offset_mlp_forward_bf16x3_nb";
+  switch (gsr::mlp_nto(who, nb)) {
+    case 1: return gsr::mlp_forward_bf16x3<1>(who, P, xyz, packed, out, stream);
+    case 2: return gsr::mlp_forward_bf16x3<2>(who, P, xyz, packed, out, stream);
+    default: return GSR_EINVAL;
+  }
+}
+
+int gsr_lbs_offset_mlp_backward_nb(int nb, int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
+                                   float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream) {
+  static const char *who = "gsr_lbs_offset_mlp_backward_nb";
+  switch (gsr::mlp_nto(who, nb)) {
+    case 1: return gsr::mlp_backward<1>(who, P, xyz, packed, dL_dout, workspace, dL_dweights, dL_dbiases, stream);
+    case 2: return gsr::mlp_backward<2>(who, P, xyz, packed, dL_dout, workspace, dL_dweights, dL_dbiases, stream);
+    default: return GSR_EINVAL;
+  }
 }
 
 }  // extern "C"

@@ -118,7 +118,7 @@ def view_camera(body, W, H, view, n_views=8, device="cuda", radius=2.4, fov_deg=
 def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="affine", body="smpl"):
     """(model, body arrays).  model.SMPL_NEUTRAL holds the body tables as device tensors; motion=True attaches the two decoders
     (decoder = "affine": the 3 x J stand-in; "reference_size": nets.FusedLBSOffsetDecoder -- the reference network's layers,
-    random init -- on the fused kernels (torch ops at J != 24); "reference_size_torch": the same module in torch ops).
+    random init -- on the fused kernels (at both J = 24 and 55); "reference_size_torch": the same module in torch ops).
     body: "smpl" (default, 24 joints) or "smplx" (55 joints); V = None: the body's own vertex count."""
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
     kind = body
@@ -136,7 +136,7 @@ def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="
             net = FusedLBSOffsetDecoder(nj).to(device)
             with torch.no_grad():
                 net.bw_fc.weight.mul_(0.05)      # small offsets around the SMPL weights, like a network early in training
-            net.use_fused = decoder == "reference_size" and nj == net.FUSED_BONES
+            net.use_fused = decoder == "reference_size"   # (nj is 24 or 55: both in nets.FUSED_BONE_COUNTS)
             model.lweight_offset_decoder = net
         else:
             model.lweight_offset_decoder = LbsOffsetDecoder(joints=nj).to(device)

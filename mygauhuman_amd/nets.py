@@ -11,9 +11,10 @@ in registers, the accuracy of the torch ops) and the backward two (the forward a
 weight gradients as products over the points).  render() hands the positions in DETACHED (:104): a `pts` that requires grad takes
 the same arithmetic in torch ops instead (forward_torch).  Tensors must live on the GPU: there is no CPU path for the fused kernels.
 
-The fused kernels are built for the 24 SMPL joints (csrc/mlp.hip packs the output layer as one 32-row tile).  Any other bone count --
-SMPL-X's 55 -- builds the reference's layer shapes (bw_fc = Conv1d(128, total_bones)) and runs forward_torch: the reference's
-arithmetic in torch ops, use_fused False.
+The fused kernels are built for the bone counts in FUSED_BONE_COUNTS: SMPL's 24 and SMPL-X's 55 (csrc/mlp.hip packs the output
+layer as one or two 32-row tiles).  FusedLBSOffsetDecoder switches them on by default at 24 only; at 55 set use_fused, or use
+LBSOffsetDecoder -- the reference's class name, which install_dropin(nets=True) hands to scene/gaussian_model.py:27 -- which switches
+them on at both.  Any other bone count builds the reference's layer shapes (bw_fc = Conv1d(128, total_bones)) and runs forward_torch.
 """
 import ctypes as C
 
@@ -22,6 +23,7 @@ import torch
 from ._lib import check, lib, ptr
 
 _OCTAVES = 10
+FUSED_BONE_COUNTS = (24, 55)   # the output widths csrc/mlp.hip is compiled for (one or two 32-row tiles)
 
 
 def set_precision(mode):
@@ -38,7 +40,11 @@ def positional_embedding(x):
 
 
 class FusedLBSOffsetDecoder(torch.nn.Module):
-    FUSED_BONES = 24   # the output width the fused kernels are built for
+    FUSED_BONES = 24   # the bone count at which use_fused is on by default
+    # class-level defaults: a module restored by pickle without them (GaussianModel.capture() pickles the decoder; __getstate__
+    # drops the device-side cache) still runs
+    use_fused = False
+    _packed, _packed_key = None, None
 
     def __init__(self, total_bones=24):
         super().__init__()
@@ -50,8 +56,14 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
                                                torch.nn.Conv1d(W + E, W, 1)])
         self.bw_fc = torch.nn.Conv1d(W, total_bones, 1)
         self._packed, self._packed_key = None, None
-        # False: the same arithmetic in torch ops (forward_torch), for comparison -- and the only path at total_bones != 24
+        # False: the same arithmetic in torch ops (forward_torch), for comparison -- and the only path outside FUSED_BONE_COUNTS
         self.use_fused = total_bones == self.FUSED_BONES
+
+    def __getstate__(self):
+        state = super().__getstate__().copy()
+        state.pop("_packed", None)       # a device buffer derived from the parameters: re-packed on the first fused call
+        state.pop("_packed_key", None)
+        return state
 
     def _layers(self):
         return list(self.bw_linears) + [self.bw_fc]
@@ -64,7 +76,8 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
             for t in ts:
                 if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                     raise RuntimeError("FusedLBSOffsetDecoder: parameters must be contiguous float32 tensors on a HIP device")
-            self._packed = _pack(ts, dev, None if (self._packed is None or self._packed.device != dev) else self._packed)
+            self._packed = _pack(self.total_bones, ts, dev,
+                                 None if (self._packed is None or self._packed.device != dev) else self._packed)
             self._packed_key = key
         return self._packed
 
@@ -80,48 +93,52 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
 
     def forward(self, pts):
         """pts [1, P, 3] -> [1, total_bones, P]."""
-        if not self.use_fused or self.total_bones != self.FUSED_BONES or (torch.is_grad_enabled() and pts.requires_grad):
+        nb = self.total_bones
+        if not self.use_fused or nb not in FUSED_BONE_COUNTS or (torch.is_grad_enabled() and pts.requires_grad):
             return self.forward_torch(pts)   # (an input gradient is not built: render() detaches the positions)
         if not pts.is_cuda:
+            if nb != self.FUSED_BONES:
+                return self.forward_torch(pts)   # (at 55 bones a CPU input has always taken the torch ops)
             raise RuntimeError("FusedLBSOffsetDecoder: tensors must live on a HIP device (no CPU path)")
         x = pts[0].detach().contiguous().float()
         params = [t for m in self._layers() for t in (m.weight, m.bias)]
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return _FusedOffsetNet.apply(x, *params).t()[None]
-        return _forward_fused(x, self._packed_weights(x.device)).t()[None]
+            return _FusedOffsetNet.apply(x, nb, *params).t()[None]
+        return _forward_fused(nb, x, self._packed_weights(x.device)).t()[None]
 
 
-def _pack(params, dev, out=None):
-    n = int(lib.gsr_lbs_offset_mlp_packed_floats())
-    packed = torch.empty(n, dtype=torch.float32, device=dev) if out is None else out
+def _pack(nb, params, dev, out=None):
+    n = int(lib.gsr_lbs_offset_mlp_packed_floats_nb(nb))
+    packed = torch.empty(n, dtype=torch.float32, device=dev) if out is None or out.numel() != n else out
     mk = lambda xs: (C.c_void_p * 5)(*[x.data_ptr() for x in xs])  # noqa: E731  (host arrays of device pointers)
     with torch.cuda.device(dev):
-        check(lib.gsr_lbs_offset_mlp_pack(mk(params[0::2]), mk(params[1::2]), ptr(packed), torch.cuda.current_stream(dev).cuda_stream),
-              "gsr_lbs_offset_mlp_pack")
+        check(lib.gsr_lbs_offset_mlp_pack_nb(nb, mk(params[0::2]), mk(params[1::2]), ptr(packed), torch.cuda.current_stream(dev).cuda_stream),
+              "gsr_lbs_offset_mlp_pack_nb")
     return packed
 
 
-def _forward_fused(x, packed):
-    out = torch.empty((x.shape[0], 24), dtype=torch.float32, device=x.device)
+def _forward_fused(nb, x, packed):
+    out = torch.empty((x.shape[0], nb), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        check(lib.gsr_lbs_offset_mlp_forward(x.shape[0], ptr(x), ptr(packed), ptr(out), torch.cuda.current_stream(x.device).cuda_stream),
-              "gsr_lbs_offset_mlp_forward")
+        check(lib.gsr_lbs_offset_mlp_forward_nb(nb, x.shape[0], ptr(x), ptr(packed), ptr(out), torch.cuda.current_stream(x.device).cuda_stream),
+              "gsr_lbs_offset_mlp_forward_nb")
     return out
 
 
 class _FusedOffsetNet(torch.autograd.Function):
-    """x [P, 3] (no gradient), the ten parameter tensors -> [P, 24]; backward = gsr_lbs_offset_mlp_backward."""
+    """x [P, 3] (no gradient), nb, the ten parameter tensors -> [P, nb]; backward = gsr_lbs_offset_mlp_backward_nb."""
 
     @staticmethod
-    def forward(ctx, x, *params):
+    def forward(ctx, x, nb, *params):
         ps = [p.detach() for p in params]
         for t in ps:
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                 raise RuntimeError("FusedLBSOffsetDecoder: parameters must be contiguous float32 tensors on a HIP device")
-        packed = _pack(ps, x.device)   # a buffer of its own: it must still describe THESE parameters when backward runs
+        packed = _pack(nb, ps, x.device)   # a buffer of its own: it must still describe THESE parameters when backward runs
         ctx.save_for_backward(x, packed)
         ctx.shapes = [tuple(p.shape) for p in params]
-        return _forward_fused(x, packed)
+        ctx.nb = nb
+        return _forward_fused(nb, x, packed)
 
     @staticmethod
     def backward(ctx, g):
@@ -135,12 +152,20 @@ class _FusedOffsetNet(torch.autograd.Function):
         for shp, n in zip(ctx.shapes, sizes):
             grads.append(flat[off:off + n].view(shp))
             off += n
-        ws = torch.empty(int(lib.gsr_lbs_offset_mlp_backward_workspace_floats(P)), dtype=torch.float32, device=dev)
+        nb = ctx.nb
+        ws = torch.empty(int(lib.gsr_lbs_offset_mlp_backward_workspace_floats_nb(nb, P)), dtype=torch.float32, device=dev)
         mk = lambda xs: (C.c_void_p * 5)(*[t.data_ptr() for t in xs])  # noqa: E731
         with torch.cuda.device(dev):
-            check(lib.gsr_lbs_offset_mlp_backward(P, ptr(x), ptr(packed), ptr(g), ptr(ws), mk(grads[0::2]), mk(grads[1::2]),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_offset_mlp_backward")
-        return (None, *grads)
+            check(lib.gsr_lbs_offset_mlp_backward_nb(nb, P, ptr(x), ptr(packed), ptr(g), ptr(ws), mk(grads[0::2]), mk(grads[1::2]),
+                                                     torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_offset_mlp_backward_nb")
+        return (None, None, *grads)
 
 
-LBSOffsetDecoder = FusedLBSOffsetDecoder   # the reference's class name (`from nets.mlp_delta_weight_lbs import LBSOffsetDecoder`)
+class LBSOffsetDecoder(FusedLBSOffsetDecoder):
+    """The reference's class name (`from nets.mlp_delta_weight_lbs import LBSOffsetDecoder`, scene/gaussian_model.py:27) with its
+    constructor and state_dict keys: the fused kernels on for every bone count they are built for (GaussianModel's SMPL-X default,
+    55, included)."""
+
+    def __init__(self, total_bones=24):
+        super().__init__(total_bones)
+        self.use_fused = total_bones in FUSED_BONE_COUNTS
