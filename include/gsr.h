@@ -660,6 +660,60 @@ size_t gsr_lbs_offset_mlp_backward_workspace_floats_nb(int nb, int P);
 int gsr_lbs_offset_mlp_backward_nb(int nb, int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
                                    float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream);
 
+/* ---- Image-based lighting (pbr/light.py, pbr/shade.py; csrc/pbr.hip; the sampling rules are in DESIGN.md "PBR stage") ----
+ * A texture is one 2-D image [h][w][C] looked up by uv with the clamp boundary, or a cube map [6][n][n][C] (face order +x -x +y
+ * -y +z -z, face-local axes of pbr/light.py cube_to_dir) looked up by direction with bilinear filtering across face edges, each
+ * with a list of `levels` mip levels selected by a per-lookup level (mip_level_bias, clamped to [0, levels-1], trilinear).
+ * grad[l] (backward only; null = not wanted) is ADDED into: zero it first. */
+#define GSR_PBR_MAX_LEVELS 16
+typedef struct gsr_pbr_texture {
+  int cube;     /* 1: cube map (coords [n][3] directions), 0: 2-D image (coords [n][2] uv) */
+  int channels; /* 1..4 */
+  int levels;   /* 1..GSR_PBR_MAX_LEVELS */
+  int width[GSR_PBR_MAX_LEVELS], height[GSR_PBR_MAX_LEVELS]; /* cube: width == height == the face size */
+  const float *data[GSR_PBR_MAX_LEVELS];
+  float *grad[GSR_PBR_MAX_LEVELS];
+} gsr_pbr_texture;
+
+/* nvdiffrast.torch.texture for the reference's call shapes: out[n][C]; mip_bias [n] may be null (level 0).  The backward writes
+ * d_coords ([n][2], 2-D textures only; may be null) and d_bias ([n]; may be null) and adds into tex->grad[]. */
+int gsr_pbr_texture_forward(const gsr_pbr_texture *tex, int n, const float *coords, const float *mip_bias, float *out,
+                            gsr_stream_t stream);
+int gsr_pbr_texture_backward(const gsr_pbr_texture *tex, int n, const float *coords, const float *mip_bias, const float *d_out,
+                             float *d_coords, float *d_bias, gsr_stream_t stream);
+
+/* CubemapLight.build_mips: fine [6][n][n][C] (n even) -> coarse [6][n/2][n/2][C], the 2x2 average; its backward is the
+ * reference's own (pbr/light.py cubemap_mip.backward, not the adjoint): d_fine at each fine texel-centre direction is the cube
+ * lookup of 0.25 * d_coarse.  d_fine is written. */
+int gsr_pbr_cube_mip_forward(int n, int channels, const float *fine, float *coarse, gsr_stream_t stream);
+int gsr_pbr_cube_mip_backward(int n, int channels, const float *d_coarse, float *d_fine, gsr_stream_t stream);
+/* diffuse_cubemap / specular_cubemap (3 channels, [6][n][n][3] -> same size), brute force over every input texel.  The specular
+ * forward writes out = rgb / wsum and wsum [6][n][n] (the backward needs it); backward outputs are written. */
+int gsr_pbr_diffuse_forward(int n, const float *cube, float *out, gsr_stream_t stream);
+int gsr_pbr_diffuse_backward(int n, const float *d_out, float *d_cube, gsr_stream_t stream);
+int gsr_pbr_specular_forward(int n, float roughness, float costheta_cutoff, const float *cube, float *out, float *wsum,
+                             gsr_stream_t stream);
+int gsr_pbr_specular_backward(int n, float roughness, float costheta_cutoff, const float *wsum, const float *d_out,
+                              float *d_cube, gsr_stream_t stream);
+
+/* pbr_shading (pbr/shade.py:105-213) over n pixels, one kernel forward and one backward.  diffuse: light.diffuse (the raw cube;
+ * the kernel applies pow(1/2.2) and the clamp per tap), specular: light.specular[0..L-1], lut: the BRDF LUT (2-D, 2 channels,
+ * channel 0 is read).  Normals and view directions take no gradient. */
+typedef struct gsr_pbr_shade {
+  int n;
+  int tone, gamma;
+  const float *normals, *view_dirs, *albedo;   /* [n][3] */
+  const float *roughness, *mask;               /* [n] */
+  const float *occlusion, *metallic;           /* [n] or null */
+  const float *background;                     /* [n][3] or null (zeros) */
+  gsr_pbr_texture diffuse, specular, lut;
+  float *render_rgb, *diffuse_rgb, *specular_rgb, *diffuse_light;                  /* forward outputs [n][3] */
+  const float *d_render_rgb, *d_diffuse_rgb, *d_specular_rgb, *d_diffuse_light;  /* backward inputs [n][3], each may be null */
+  float *d_albedo, *d_roughness, *d_occlusion, *d_metallic;                      /* backward outputs (written), each may be null */
+} gsr_pbr_shade;
+int gsr_pbr_shade_forward(const gsr_pbr_shade *s, gsr_stream_t stream);
+int gsr_pbr_shade_backward(const gsr_pbr_shade *s, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

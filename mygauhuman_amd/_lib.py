@@ -23,6 +23,26 @@ class Phase1LossStruct(C.Structure):
                 ("color", C.c_void_p), ("alpha", C.c_void_p), ("extra_images", C.c_void_p), ("stats", C.c_void_p),
                 ("upstream", C.c_void_p)]
 
+PBR_MAX_LEVELS = 16
+
+
+class PbrTexture(C.Structure):
+    """gsr_pbr_texture (include/gsr.h): one 2-D texture or cube map with its mip levels (and their gradient buffers)."""
+    _fields_ = [("cube", C.c_int), ("channels", C.c_int), ("levels", C.c_int),
+                ("width", C.c_int * PBR_MAX_LEVELS), ("height", C.c_int * PBR_MAX_LEVELS),
+                ("data", C.c_void_p * PBR_MAX_LEVELS), ("grad", C.c_void_p * PBR_MAX_LEVELS)]
+
+
+class PbrShade(C.Structure):
+    """gsr_pbr_shade (include/gsr.h): the fused pbr_shading pass."""
+    _fields_ = [("n", C.c_int), ("tone", C.c_int), ("gamma", C.c_int)] + \
+        [(k, C.c_void_p) for k in ("normals", "view_dirs", "albedo", "roughness", "mask", "occlusion", "metallic", "background")] + \
+        [("diffuse", PbrTexture), ("specular", PbrTexture), ("lut", PbrTexture)] + \
+        [(k, C.c_void_p) for k in ("render_rgb", "diffuse_rgb", "specular_rgb", "diffuse_light",
+                                   "d_render_rgb", "d_diffuse_rgb", "d_specular_rgb", "d_diffuse_light",
+                                   "d_albedo", "d_roughness", "d_occlusion", "d_metallic")]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -34,6 +54,9 @@ SYMBOLS = [
     "gsr_lbs_forward_nj", "gsr_lbs_forward_grid_nj", "gsr_lbs_forward_cached_nj", "gsr_lbs_backward_nj", "gsr_body_pose_forward",
     "gsr_body_pose_backward", "gsr_lbs_offset_mlp_packed_floats_nb", "gsr_lbs_offset_mlp_pack_nb", "gsr_lbs_offset_mlp_forward_nb",
     "gsr_debug_lbs_offset_mlp_forward_bf16x3_nb", "gsr_lbs_offset_mlp_backward_workspace_floats_nb", "gsr_lbs_offset_mlp_backward_nb",
+    "gsr_pbr_texture_forward", "gsr_pbr_texture_backward", "gsr_pbr_cube_mip_forward", "gsr_pbr_cube_mip_backward",
+    "gsr_pbr_diffuse_forward", "gsr_pbr_diffuse_backward", "gsr_pbr_specular_forward", "gsr_pbr_specular_backward",
+    "gsr_pbr_shade_forward", "gsr_pbr_shade_backward",
 ]
 
 GSR_OK = 0
@@ -186,6 +209,17 @@ def _load():
                  "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward"):
         getattr(lib, name + "_nb").argtypes = [C.c_int] + getattr(lib, name).argtypes
         getattr(lib, name + "_nb").restype = getattr(lib, name).restype
+    pt = C.POINTER(PbrTexture)
+    lib.gsr_pbr_texture_forward.argtypes = [pt, C.c_int, fp, fp, fp, vp]
+    lib.gsr_pbr_texture_backward.argtypes = [pt, C.c_int, fp, fp, fp, fp, fp, vp]
+    lib.gsr_pbr_cube_mip_forward.argtypes = lib.gsr_pbr_cube_mip_backward.argtypes = [C.c_int, C.c_int, fp, fp, vp]
+    lib.gsr_pbr_diffuse_forward.argtypes = lib.gsr_pbr_diffuse_backward.argtypes = [C.c_int, fp, fp, vp]
+    lib.gsr_pbr_specular_forward.argtypes = [C.c_int, C.c_float, C.c_float, fp, fp, fp, vp]
+    lib.gsr_pbr_specular_backward.argtypes = [C.c_int, C.c_float, C.c_float, fp, fp, fp, vp]
+    lib.gsr_pbr_shade_forward.argtypes = lib.gsr_pbr_shade_backward.argtypes = [C.POINTER(PbrShade), vp]
+    for name in ("texture_forward", "texture_backward", "cube_mip_forward", "cube_mip_backward", "diffuse_forward",
+                 "diffuse_backward", "specular_forward", "specular_backward", "shade_forward", "shade_backward"):
+        getattr(lib, "gsr_pbr_" + name).restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

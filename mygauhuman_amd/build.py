@@ -32,6 +32,7 @@ SOURCES = [
     ("loss.hip", []),
     ("probe.hip", []),
     ("mlp.hip", []),
+    ("pbr.hip", []),
     ("gsr_api.hip", []),
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
