@@ -714,6 +714,38 @@ typedef struct gsr_pbr_shade {
 int gsr_pbr_shade_forward(const gsr_pbr_shade *s, gsr_stream_t stream);
 int gsr_pbr_shade_backward(const gsr_pbr_shade *s, gsr_stream_t stream);
 
+/* ---- Occlusion bake (baking.py bake_set; csrc/bake.hip; DESIGN.md "Occlusion bake") ----
+ * gsr_bake_grid is pc_to_grid(points, 10): cell[P] = the compact cell id of each point, the occupied cells numbered in (ix, iy, iz)
+ * lexicographic order (torch.unique's), centres[n][3] and cell_idx[n][3] (may be null) for the first *n_cells of 1000 rows, size[3]
+ * (may be null).  A zero-extent axis puts every point at index 0 there.  *n_cells is read to the host (the call blocks).
+ * gsr_bake_plan computes the view-independent cov3D, the needed cube texels (dir_texel: face * 1024 + y * 32 + x per direction)
+ * and every (cell, face, tile) instance count into `plan` (kept for gsr_bake_visibility), and returns instances[0] = all of
+ * them, instances[1] = the largest cell's (blocks).  gsr_bake_visibility writes vis[C][ndir] = 1 - the rasterizer's alpha (sum of
+ * alpha T) at each direction's texel of cell c's cube, rendered without cell c's Gaussians; it processes cells in batches that fit
+ * the workspace (20 bytes per instance beside gsr_bake_visibility_workspace_bytes(C, 0); tuning key "bake_batch_cells" caps a
+ * batch) and fills stats[4] (may be null): instances, largest batch, batches, capacity. */
+typedef struct gsr_bake_scene {
+  int P, C;                                            /* Gaussians, occupied cells */
+  const float *means3D, *scales, *rotations, *opacities; /* [P][3] posed means, [P][3] / [P][4] canonical scales / rotations, [P] */
+  const int *cell;                                     /* [P] from gsr_bake_grid */
+  const float *views, *projs;                          /* [C][6][16] world-view and full projection matrices (the rasterizer's) */
+  const int *dir_texel;                                /* [ndir] */
+  int ndir;
+} gsr_bake_scene;
+size_t gsr_bake_grid_workspace_bytes(void);
+int gsr_bake_grid(int P, const float *points, int *cell, float *centres, float *size, int *cell_idx, int *n_cells, void *workspace,
+                  size_t workspace_bytes, gsr_stream_t stream);
+size_t gsr_bake_plan_bytes(int P, int C);
+int gsr_bake_plan(const gsr_bake_scene *scene, void *plan, size_t plan_bytes, unsigned long long *instances, gsr_stream_t stream);
+size_t gsr_bake_visibility_workspace_bytes(int C, size_t capacity);
+int gsr_bake_visibility(const gsr_bake_scene *scene, const void *plan, float *vis, void *workspace, size_t workspace_bytes,
+                        unsigned long long *stats, gsr_stream_t stream);
+/* occ[P][ndir] = (dirs[d] . normals[p] > 0) * vis[cell[p]][d], the dot summed left to right without contraction */
+int gsr_bake_expand(int P, int ndir, const int *cell, const float *normals, const float *dirs, const float *vis, float *occ,
+                    gsr_stream_t stream);
+/* out[P][3] = clamp(sum_d clamp(occ[p][d], 0, 1) * env[d], 0, 1) over 512 directions (16-byte aligned occ and env) */
+int gsr_bake_env_reduce(int P, const float *occ, const float *env, float *out, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

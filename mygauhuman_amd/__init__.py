@@ -7,6 +7,7 @@ mirrors the reference's operator surface:
   mygauhuman_amd.simple_knn._C.distCUDA2      <- submodules/simple-knn
   mygauhuman_amd.gaussian_renderer.render     <- gaussian_renderer/__init__.py
   mygauhuman_amd.pbr, mygauhuman_amd.nvdiffrast <- pbr/ (CubemapLight, pbr_shading) and nvdiffrast.torch.texture
+  mygauhuman_amd.baking                       <- baking.py (bake_set: per-Gaussian occlusion)
 
 `install_dropin()` registers those modules under the reference's import names so train.py / render.py style
 callers work unmodified.
@@ -31,7 +32,7 @@ GRAPH_REPLAY_SAFE = os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
 __version__ = "0.1.0"
 
 
-def install_dropin(render=False, nets=False, pbr=False):
+def install_dropin(render=False, nets=False, pbr=False, bake=False):
     """Make `import diff_gaussian_rasterization`, `from simple_knn._C import distCUDA2`, `from knn_cuda import KNN` resolve
     to this package.  render=True also registers `gaussian_renderer` (train.py:17 / render.py import `render` -- and train.py
     `network_gui` -- from it), so that the reference's own drivers reach the fused render() without an edit; the reference's
@@ -39,7 +40,8 @@ def install_dropin(render=False, nets=False, pbr=False):
     (scene/gaussian_model.py:27 imports LBSOffsetDecoder from it): the skinning-offset network on the fused kernels, same
     constructor, same state_dict keys.  pbr=True registers `pbr` (train.py / render.py: CubemapLight, get_brdf_lut, pbr_shading)
     and `nvdiffrast` / `nvdiffrast.torch` (texture() for the reference's call shapes): the image-based-lighting stage on the
-    fused kernels of csrc/pbr.hip."""
+    fused kernels of csrc/pbr.hip.  bake=True registers `baking` (bake_set on the kernels of csrc/bake.hip) and turns on baking
+    in render(): at iteration > 30000 a camera without `occlusion` is baked and keeps it."""
     pairs = [("diff_gaussian_rasterization", "mygauhuman_amd.diff_gaussian_rasterization"),
              ("simple_knn", "mygauhuman_amd.simple_knn"),
              ("simple_knn._C", "mygauhuman_amd.simple_knn._C"),
@@ -52,5 +54,9 @@ def install_dropin(render=False, nets=False, pbr=False):
     if pbr:
         pairs += [("pbr", "mygauhuman_amd.pbr"), ("pbr.light", "mygauhuman_amd.pbr.light"), ("pbr.shade", "mygauhuman_amd.pbr.shade"),
                   ("nvdiffrast", "mygauhuman_amd.nvdiffrast"), ("nvdiffrast.torch", "mygauhuman_amd.nvdiffrast.torch")]
+    if bake:
+        pairs += [("baking", "mygauhuman_amd.baking")]
     for theirs, ours in pairs:
         sys.modules[theirs] = importlib.import_module(ours)
+    if bake:
+        importlib.import_module("mygauhuman_amd.gaussian_renderer").BAKE = True

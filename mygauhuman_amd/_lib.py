@@ -43,6 +43,12 @@ class PbrShade(C.Structure):
                                    "d_albedo", "d_roughness", "d_occlusion", "d_metallic")]
 
 
+class BakeScene(C.Structure):
+    """gsr_bake_scene (include/gsr.h): the inputs of the occlusion bake."""
+    _fields_ = [("P", C.c_int), ("C", C.c_int)] + [(k, C.c_void_p) for k in (
+        "means3D", "scales", "rotations", "opacities", "cell", "views", "projs", "dir_texel")] + [("ndir", C.c_int)]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -57,6 +63,8 @@ SYMBOLS = [
     "gsr_pbr_texture_forward", "gsr_pbr_texture_backward", "gsr_pbr_cube_mip_forward", "gsr_pbr_cube_mip_backward",
     "gsr_pbr_diffuse_forward", "gsr_pbr_diffuse_backward", "gsr_pbr_specular_forward", "gsr_pbr_specular_backward",
     "gsr_pbr_shade_forward", "gsr_pbr_shade_backward",
+    "gsr_bake_grid_workspace_bytes", "gsr_bake_grid", "gsr_bake_plan_bytes", "gsr_bake_plan", "gsr_bake_visibility_workspace_bytes",
+    "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
 ]
 
 GSR_OK = 0
@@ -220,6 +228,21 @@ def _load():
     for name in ("texture_forward", "texture_backward", "cube_mip_forward", "cube_mip_backward", "diffuse_forward",
                  "diffuse_backward", "specular_forward", "specular_backward", "shade_forward", "shade_backward"):
         getattr(lib, "gsr_pbr_" + name).restype = C.c_int
+    sz, u64p = C.c_size_t, C.POINTER(C.c_ulonglong)
+    bs = C.POINTER(BakeScene)
+    lib.gsr_bake_grid_workspace_bytes.argtypes = []
+    lib.gsr_bake_grid_workspace_bytes.restype = sz
+    lib.gsr_bake_grid.argtypes = [C.c_int, fp, fp, fp, fp, fp, C.POINTER(C.c_int), vp, sz, vp]
+    lib.gsr_bake_plan_bytes.argtypes = [C.c_int, C.c_int]
+    lib.gsr_bake_plan_bytes.restype = sz
+    lib.gsr_bake_plan.argtypes = [bs, vp, sz, u64p, vp]
+    lib.gsr_bake_visibility_workspace_bytes.argtypes = [C.c_int, sz]
+    lib.gsr_bake_visibility_workspace_bytes.restype = sz
+    lib.gsr_bake_visibility.argtypes = [bs, vp, fp, vp, sz, u64p, vp]
+    lib.gsr_bake_expand.argtypes = [C.c_int, C.c_int, fp, fp, fp, fp, fp, vp]
+    lib.gsr_bake_env_reduce.argtypes = [C.c_int, fp, fp, fp, vp]
+    for name in ("grid", "plan", "visibility", "expand", "env_reduce"):
+        getattr(lib, "gsr_bake_" + name).restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

@@ -33,6 +33,7 @@ SOURCES = [
     ("probe.hip", []),
     ("mlp.hip", []),
     ("pbr.hip", []),
+    ("bake.hip", ["-ffp-contract=off"]),
     ("gsr_api.hip", []),
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

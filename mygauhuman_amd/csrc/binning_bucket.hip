@@ -1136,4 +1136,22 @@ int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int 
   return GSR_OK;
 }
 
+// The per-tile sorts alone, for callers that build the buckets themselves (bake.hip: a tile space of (cell, cube face, tile)).
+// bucket[ranges[t].x .. ranges[t].y) holds tile t's keys (depth bits << 32 | Gaussian id) in any order; point_list gets the ids in
+// (depth, id) order.  keys_sorted (same length as bucket) is written, and is the merge buffer of lists longer than LDS.  big_list
+// holds `tiles` words; *big_count must be zero on entry.
+int bucket_sort_lists(const uint2 *ranges, uint64_t *bucket, uint32_t *point_list, uint64_t *keys_sorted, uint32_t *big_list,
+                      uint32_t *big_count, size_t tiles, hipStream_t stream) {
+  if (tiles == 0) return GSR_OK;
+  hipLaunchKernelGGL(bucket_sort_wave_kernel, dim3((unsigned)tiles), dim3(WAVE), 0, stream, ranges, bucket, point_list, keys_sorted,
+                     big_list, big_count);
+  GSR_LAUNCH_CHECK(stream, 0);
+  const unsigned big_grid = 4u * (unsigned)cu_count();
+  const unsigned n_big = (unsigned)(tiles < big_grid ? tiles : big_grid);
+  hipLaunchKernelGGL((bucket_sort_kernel<SORT_BIG, SORT_WAVE_MAX, true>), dim3(n_big), dim3(256), 0, stream, ranges, bucket, point_list,
+                     keys_sorted, big_list, big_count);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
 }  // namespace gsr

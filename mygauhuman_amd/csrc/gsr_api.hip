@@ -153,6 +153,9 @@ static int set_option(Options &o, const char *key, int v) {
     if (v < 0 || v > 4) return bad("0, 1 (issue priority by list length); experiments: 2..4 (MEASUREMENT ONLY: render the longest lists alone)");
     if (experiment(v >= 2)) return GSR_EINVAL;
     o.blend_prio = v;
+  } else if (!strcmp(key, "bake_batch_cells")) {
+    if (v < 0 || v > 1000) return bad("0 (as many as the workspace holds) or 1 .. 1000");
+    o.bake_batch_cells = v;
   } else if (!strcmp(key, "debug_no_atomics")) {
     if (v != 0 && v != 1) return bad("0 or 1");
     o.debug_no_atomics = v;

@@ -251,6 +251,7 @@ struct Options {
   int blend_segments = 8;    // > 0: lists of at least blend_segments / 4 x the frame's mean list are walked in segments by the backward
                              // (forward checkpoints), see ORDER_HDR; 0: never
   int blend_prio = 1;        // 1: blend waves take an issue priority from the length of their tile's list (list_priority)
+  int bake_batch_cells = 0;  // bake (bake.hip): most grid cells per batch; 0 = as many as the caller's workspace holds
   int debug_no_atomics = 0;  // MEASUREMENT ONLY: the plain blend backward without its gradient-row atomics (gradients are wrong)
 };
 Options options_for(hipStream_t stream);
@@ -412,6 +413,9 @@ int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int 
                    bool check_prefilter, bool scan_fused, const Options &opt, hipStream_t stream, int debug);
 // true if bucket_binning will take its atomics-free histogram path (which can also do the block-sums scan: scan_fused)
 bool bucket_uses_hist(const Options &opt, int P, size_t tiles, size_t capacity);
+// the per-tile sorts of the tile-bucket back-end over caller-built buckets (see binning_bucket.hip)
+int bucket_sort_lists(const uint2 *ranges, uint64_t *bucket, uint32_t *point_list, uint64_t *keys_sorted, uint32_t *big_list,
+                      uint32_t *big_count, size_t tiles, hipStream_t stream);
 
 }  // namespace gsr
 

@@ -17,7 +17,7 @@ class); `viewpoint_camera` exposes FoVx, FoVy, image_height, image_width, world_
 camera_center, smpl_param, big_pose_smpl_param, big_pose_world_vertex (scene/cameras.py:17-74) and optionally
 `occlusion`.  The post-30k-iteration occlusion baking (baking.py, nvdiffrast) is outside the hot path: pass
 `viewpoint_camera.occlusion` if you have it, otherwise the opacity-derived placeholder of the reference's first 30k
-iterations is used (:141).
+iterations is used (:141) -- unless install_dropin(bake=True) turned on baking (BAKE below, mygauhuman_amd.baking).
 """
 import math
 import os
@@ -76,6 +76,10 @@ def _features_of(pc):
 # accumulation kernels of autograd; GSR_GRAD_LINK=0 keeps autograd's own accumulation
 GRAD_LINK = os.environ.get("GSR_GRAD_LINK", "1") != "0"
 
+# install_dropin(bake=True): at iteration > 30000 a camera without `occlusion` is baked (mygauhuman_amd.baking) and cached on it, and
+# the occlusion colours against an envmap come from one HIP kernel.  Off by default: the opacity placeholder as before.
+BAKE = False
+
 
 def render(iteration, viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None,
            return_smpl_rot=False, transforms=None, translation=None, envmap=None, fused_loss=None):
@@ -130,9 +134,20 @@ def _render_frame(iteration, viewpoint_camera, pc, pipe, bg_color, scaling_modif
     scaling = act.scaling if act is not None else pc.get_scaling
     rotation_n = act.rotation if act is not None else pc.get_rotation
     occlusion = getattr(viewpoint_camera, "occlusion", None)
+    if iteration > 30000 and occlusion is None and BAKE:
+        # :152-165: a camera without an occlusion is baked once and keeps it (mygauhuman_amd.baking, csrc/bake.hip)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("render(): the camera has no occlusion and a bake cannot run inside a graph capture; bake it first "
+                               "(baking.bake_set, or one eager render() at iteration > 30000)")
+        from ..baking import bake_set
+        wn = world_normal.detach().reshape(-1, 3)
+        occlusion = bake_set(viewpoint_camera, pc, means3D.detach(), wn / wn.norm(dim=1, keepdim=True), H=16, W=32)
     if iteration > 30000 and occlusion is not None:
         occlusion = occlusion.detach()
-        if envmap is not None:
+        if envmap is not None and BAKE:
+            from ..baking import env_occlusion
+            _occlusion = env_occlusion(occlusion, envmap)  # one HIP kernel for the expression below
+        elif envmap is not None:
             occ = torch.clamp(occlusion, min=0, max=1) * envmap.permute(1, 2, 0)
             _occlusion = occ.sum(dim=(1, 2)).repeat(1, 3).clamp(min=0.0, max=1.0)
         else:
