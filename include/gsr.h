@@ -746,6 +746,45 @@ int gsr_bake_expand(int P, int ndir, const int *cell, const float *normals, cons
 /* out[P][3] = clamp(sum_d clamp(occ[p][d], 0, 1) * env[d], 0, 1) over 512 directions (16-byte aligned occ and env) */
 int gsr_bake_env_reduce(int P, const float *occ, const float *env, float *out, gsr_stream_t stream);
 
+/* ---- PBR-phase training loss (train.py:296-363 less SSIM, LPIPS and the env-map TV; csrc/pbr_loss.hip) ----
+ * Every image is [C][H][W] float32, contiguous, except rgb, which is read (and d_rgb written) at the element strides rgb_stride.
+ * Each term is optional: its inputs null (or its flag 0) turn it off, its unweighted value is then 0 and it adds nothing.
+ *   terms[0] L1:      mean |rgb - gt| over the 3 * n_b values whose pixel has bound == 1 (n_b = 0: NaN, gradient 0)
+ *   terms[1] TV:      masked TV of [a; b] (ca + cb channels) under mask, masked-out entries in the denominators; mask takes a gradient
+ *   terms[2] entropy: gaussian_entropy of a ([ca * H][W] view, entropy[0]) plus that of b (entropy[1]): columns 0..2 only, sigma =
+ *                     the unbiased variance, a column whose histogram sum is not > 1e-6 adds 0 and gets a zero gradient; W >= 3
+ *   terms[3] smooth:  sum over t of mean_{P, gc[t]} |g[t][k1] - g[t][k2]| / (g[t][k2] + 1e-6)
+ *   terms[4] prior:   mean of 1 - b[0] over the n_a pixels with mask > 0 (n_a = 0: NaN, gradient 0); mask takes no gradient
+ * loss = sum of w * term.  The forward writes loss, terms and, in `workspace` (gsr_pbr_loss_workspace_floats() floats), the
+ * per-workgroup partials and the coefficients the backward reads; nothing is read to the host and no float atomics are used, so
+ * two calls give the same bits.  The backward multiplies by *upstream (null: 1) read on the device and writes each non-null d_*
+ * in full; the smoothness gradient gathers each row's contributions through inv_off / inv_idx (the entries p sorted stably by
+ * k1[p], and by k2[p]: offsets [P + 1], entry ids [P]). */
+typedef struct gsr_pbr_loss {
+  int width, height;
+  const float *rgb;                   /* [3][H][W] at rgb_stride (channel, row, column; elements) */
+  long long rgb_stride[3];
+  const float *gt, *bound;            /* [3][H][W], [H][W] */
+  const float *a, *b, *mask;          /* [ca][H][W], [cb][H][W] (or null), [H][W] */
+  int ca, cb;
+  int tv, entropy[2], prior;          /* term flags */
+  int bins;                           /* histogram bins, 1..32, centres lo + (k + 0.5) * (hi - lo) / bins */
+  float lo, hi;
+  int P;                              /* smoothness: P rows, k1 / k2 [P] in [0, P) */
+  const int *k1, *k2;
+  const float *g[2];                  /* [P][gc[t]] or null */
+  int gc[2];
+  const int *inv_off[2], *inv_idx[2]; /* [0]: by k1, [1]: by k2 (backward only) */
+  float w_l1, w_tv, w_entropy, w_smooth, w_prior;
+  float *loss, *terms;                /* [1], [5] */
+  const float *upstream;              /* backward: [1] or null */
+  float *d_rgb, *d_a, *d_b, *d_mask;  /* backward outputs, each may be null */
+  float *d_g[2];
+} gsr_pbr_loss;
+size_t gsr_pbr_loss_workspace_floats(void);
+int gsr_pbr_loss_forward(const gsr_pbr_loss *loss, float *workspace, gsr_stream_t stream);
+int gsr_pbr_loss_backward(const gsr_pbr_loss *loss, const float *workspace, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,18 @@ class BakeScene(C.Structure):
         "means3D", "scales", "rotations", "opacities", "cell", "views", "projs", "dir_texel")] + [("ndir", C.c_int)]
 
 
+class PbrLoss(C.Structure):
+    """gsr_pbr_loss (include/gsr.h): the fused PBR-phase training loss."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("rgb", C.c_void_p), ("rgb_stride", C.c_longlong * 3),
+                ("gt", C.c_void_p), ("bound", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("mask", C.c_void_p),
+                ("ca", C.c_int), ("cb", C.c_int), ("tv", C.c_int), ("entropy", C.c_int * 2), ("prior", C.c_int),
+                ("bins", C.c_int), ("lo", C.c_float), ("hi", C.c_float),
+                ("P", C.c_int), ("k1", C.c_void_p), ("k2", C.c_void_p), ("g", C.c_void_p * 2), ("gc", C.c_int * 2),
+                ("inv_off", C.c_void_p * 2), ("inv_idx", C.c_void_p * 2)] + \
+        [(k, C.c_float) for k in ("w_l1", "w_tv", "w_entropy", "w_smooth", "w_prior")] + \
+        [(k, C.c_void_p) for k in ("loss", "terms", "upstream", "d_rgb", "d_a", "d_b", "d_mask")] + [("d_g", C.c_void_p * 2)]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -65,6 +77,7 @@ SYMBOLS = [
     "gsr_pbr_shade_forward", "gsr_pbr_shade_backward",
     "gsr_bake_grid_workspace_bytes", "gsr_bake_grid", "gsr_bake_plan_bytes", "gsr_bake_plan", "gsr_bake_visibility_workspace_bytes",
     "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
+    "gsr_pbr_loss_workspace_floats", "gsr_pbr_loss_forward", "gsr_pbr_loss_backward",
 ]
 
 GSR_OK = 0
@@ -243,6 +256,11 @@ def _load():
     lib.gsr_bake_env_reduce.argtypes = [C.c_int, fp, fp, fp, vp]
     for name in ("grid", "plan", "visibility", "expand", "env_reduce"):
         getattr(lib, "gsr_bake_" + name).restype = C.c_int
+    lib.gsr_pbr_loss_workspace_floats.argtypes = []
+    lib.gsr_pbr_loss_workspace_floats.restype = sz
+    lib.gsr_pbr_loss_forward.argtypes = [C.POINTER(PbrLoss), fp, vp]
+    lib.gsr_pbr_loss_backward.argtypes = [C.POINTER(PbrLoss), fp, vp]
+    lib.gsr_pbr_loss_forward.restype = lib.gsr_pbr_loss_backward.restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

@@ -34,6 +34,7 @@ SOURCES = [
     ("mlp.hip", []),
     ("pbr.hip", []),
     ("bake.hip", ["-ffp-contract=off"]),
+    ("pbr_loss.hip", []),
     ("gsr_api.hip", []),
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

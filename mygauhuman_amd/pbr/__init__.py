@@ -1,6 +1,8 @@
 """The reference's pbr package (CubemapLight, pbr_shading, get_brdf_lut, saturate_dot) on csrc/pbr.hip; install_dropin(pbr=True)
-registers it as `pbr`."""
+registers it as `pbr`.  The PBR phase's training loss (PbrPhaseLoss and its parts) runs on csrc/pbr_loss.hip."""
 from .light import CubemapLight
+from .loss import MaterialSmoothness, PbrPhaseLoss, gaussian_entropy, get_masked_tv_loss
 from .shade import get_brdf_lut, pbr_shading, saturate_dot
 
-__all__ = ["CubemapLight", "get_brdf_lut", "pbr_shading", "saturate_dot"]
+__all__ = ["CubemapLight", "MaterialSmoothness", "PbrPhaseLoss", "gaussian_entropy", "get_brdf_lut", "get_masked_tv_loss",
+           "pbr_shading", "saturate_dot"]
