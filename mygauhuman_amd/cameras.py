@@ -43,12 +43,12 @@ def focal2fov(focal, pixels):
     return 2 * math.atan(pixels / (2 * focal))
 
 
-def make_camera(W, H, fov_deg=50.0, R=None, T=None):
-    """Pinhole camera with fx = fy = W / (2 tan(fov/2)), principal point at the image centre."""
+def camera_from_K(W, H, K, R=None, T=None):
+    """Camera of intrinsics K (3x3: fx, fy, principal point, skew K[0,1]) and pose (R, T) of getWorld2View2, with the fields
+    of scene/cameras.py:17-74 the rasterizer reads.  tan(fov/2) comes from fx and fy as in scene/cameras.py (focal2fov)."""
     R = np.eye(3) if R is None else np.asarray(R, np.float64)
     T = np.zeros(3) if T is None else np.asarray(T, np.float64)
-    f = W / (2.0 * math.tan(math.radians(fov_deg) * 0.5))
-    K = np.array([[f, 0, W / 2.0], [0, f, H / 2.0], [0, 0, 1]], np.float32)
+    K = np.asarray(K, np.float32)
     view_T = world2view(R, T).T.copy()  # world_view_transform
     proj_T = projection_from_K(K, H, W).T.copy()
     full = (view_T.astype(np.float32) @ proj_T.astype(np.float32)).astype(np.float32)
@@ -57,6 +57,13 @@ def make_camera(W, H, fov_deg=50.0, R=None, T=None):
     return dict(W=W, H=H, K=K, viewmatrix=np.ascontiguousarray(view_T, np.float32),
                 projmatrix=np.ascontiguousarray(full, np.float32), campos=campos,
                 tanfovx=math.tan(fovx * 0.5), tanfovy=math.tan(fovy * 0.5), FoVx=fovx, FoVy=fovy)
+
+
+def make_camera(W, H, fov_deg=50.0, R=None, T=None):
+    """Pinhole camera with fx = fy = W / (2 tan(fov/2)), principal point at the image centre."""
+    f = W / (2.0 * math.tan(math.radians(fov_deg) * 0.5))
+    K = np.array([[f, 0, W / 2.0], [0, f, H / 2.0], [0, 0, 1]], np.float32)
+    return camera_from_K(W, H, K, R, T)
 
 
 def look_at_camera(W, H, eye, target, fov_deg=50.0):
