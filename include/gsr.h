@@ -660,6 +660,24 @@ size_t gsr_lbs_offset_mlp_backward_workspace_floats_nb(int nb, int P);
 int gsr_lbs_offset_mlp_backward_nb(int nb, int P, const float *xyz, const float *packed, const float *dL_dout, float *workspace,
                                    float *const *dL_dweights, float *const *dL_dbiases, gsr_stream_t stream);
 
+/* The pose-correction network of render() (nets/mlp_delta_body_pose.py: BodyPoseRefiner as scene/gaussian_model.py:95 builds it --
+ * total_bones = J, embedding_size = 3(J-1), mlp_width = 128, mlp_depth = 2 -- followed by its RodriguesModule), one single-workgroup
+ * launch each way (csrc/pose_refiner.hip).  J = 24 or 55, width = 128, 1 <= B <= 16 pose rows; anything else returns GSR_EINVAL
+ * (gsr_last_error() names it) before any other argument or the device is looked at.
+ *   x: [B][3(J-1)] float32 with element strides x_row_stride / x_col_stride (a view such as poses[:, 3:] is read in place);
+ *   weights[3] / biases[3]: host arrays of DEVICE pointers to block_mlps.0 / .2 / .4 in the module's own layout (Linear weight
+ *     [out][in] row-major: [128][3(J-1)], [128][128], [3(J-1)][128]; biases [128], [128], [3(J-1)]);
+ *   gsr_pose_refiner_forward: Rs [B][J-1][3][3] = Rodrigues(r) per 3-vector of r = W4 relu(W2 relu(W0 x + b0) + b2) + b4, with
+ *     theta = sqrt(1e-5 + |r|^2) (NOT the 1e-8 rule of gsr_body_pose_forward);
+ *   gsr_pose_refiner_backward: the forward again, then dL_dRs [B][J-1][3][3] -> dL_dweights[3] / dL_dbiases[3] (host arrays of
+ *     device pointers, the module's layouts) and dL_dx [B][3(J-1)] contiguous (or null: not wanted).  Every output is written whole
+ *     (no zero fill needed), every sum has a fixed order: two calls give the same bits. */
+int gsr_pose_refiner_forward(int J, int B, int width, const float *x, long long x_row_stride, long long x_col_stride,
+                             const float *const *weights, const float *const *biases, float *Rs, gsr_stream_t stream);
+int gsr_pose_refiner_backward(int J, int B, int width, const float *x, long long x_row_stride, long long x_col_stride,
+                              const float *const *weights, const float *const *biases, const float *dL_dRs,
+                              float *const *dL_dweights, float *const *dL_dbiases, float *dL_dx, gsr_stream_t stream);
+
 /* ---- Image-based lighting (pbr/light.py, pbr/shade.py; csrc/pbr.hip; the sampling rules are in DESIGN.md "PBR stage") ----
  * A texture is one 2-D image [h][w][C] looked up by uv with the clamp boundary, or a cube map [6][n][n][C] (face order +x -x +y
  * -y +z -z, face-local axes of pbr/light.py cube_to_dir) looked up by direction with bilinear filtering across face edges, each

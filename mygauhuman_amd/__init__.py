@@ -32,7 +32,7 @@ GRAPH_REPLAY_SAFE = os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
 __version__ = "0.1.0"
 
 
-def install_dropin(render=False, nets=False, pbr=False, bake=False):
+def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner=False):
     """Make `import diff_gaussian_rasterization`, `from simple_knn._C import distCUDA2`, `from knn_cuda import KNN` resolve
     to this package.  render=True also registers `gaussian_renderer` (train.py:17 / render.py import `render` -- and train.py
     `network_gui` -- from it), so that the reference's own drivers reach the fused render() without an edit; the reference's
@@ -41,7 +41,9 @@ def install_dropin(render=False, nets=False, pbr=False, bake=False):
     constructor, same state_dict keys.  pbr=True registers `pbr` (train.py / render.py: CubemapLight, get_brdf_lut, pbr_shading)
     and `nvdiffrast` / `nvdiffrast.torch` (texture() for the reference's call shapes): the image-based-lighting stage on the
     fused kernels of csrc/pbr.hip.  bake=True registers `baking` (bake_set on the kernels of csrc/bake.hip) and turns on baking
-    in render(): at iteration > 30000 a camera without `occlusion` is baked and keeps it."""
+    in render(): at iteration > 30000 a camera without `occlusion` is baked and keeps it.  pose_refiner=True registers
+    `nets.mlp_delta_body_pose` (scene/gaussian_model.py imports BodyPoseRefiner from it): the pose-correction network on the fused
+    kernels of csrc/pose_refiner.hip (nets_pose.py), same constructor, same state_dict keys; nets=True alone leaves it alone."""
     pairs = [("diff_gaussian_rasterization", "mygauhuman_amd.diff_gaussian_rasterization"),
              ("simple_knn", "mygauhuman_amd.simple_knn"),
              ("simple_knn._C", "mygauhuman_amd.simple_knn._C"),
@@ -56,6 +58,8 @@ def install_dropin(render=False, nets=False, pbr=False, bake=False):
                   ("nvdiffrast", "mygauhuman_amd.nvdiffrast"), ("nvdiffrast.torch", "mygauhuman_amd.nvdiffrast.torch")]
     if bake:
         pairs += [("baking", "mygauhuman_amd.baking")]
+    if pose_refiner:
+        pairs += [("nets.mlp_delta_body_pose", "mygauhuman_amd.nets_pose")]
     for theirs, ours in pairs:
         sys.modules[theirs] = importlib.import_module(ours)
     if bake:

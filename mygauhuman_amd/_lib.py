@@ -78,6 +78,7 @@ SYMBOLS = [
     "gsr_bake_grid_workspace_bytes", "gsr_bake_grid", "gsr_bake_plan_bytes", "gsr_bake_plan", "gsr_bake_visibility_workspace_bytes",
     "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
     "gsr_pbr_loss_workspace_floats", "gsr_pbr_loss_forward", "gsr_pbr_loss_backward",
+    "gsr_pose_refiner_forward", "gsr_pose_refiner_backward",
 ]
 
 GSR_OK = 0
@@ -261,6 +262,11 @@ def _load():
     lib.gsr_pbr_loss_forward.argtypes = [C.POINTER(PbrLoss), fp, vp]
     lib.gsr_pbr_loss_backward.argtypes = [C.POINTER(PbrLoss), fp, vp]
     lib.gsr_pbr_loss_forward.restype = lib.gsr_pbr_loss_backward.restype = C.c_int
+    ll = C.c_longlong
+    lib.gsr_pose_refiner_forward.argtypes = [C.c_int, C.c_int, C.c_int, fp, ll, ll, C.POINTER(fp), C.POINTER(fp), fp, vp]
+    lib.gsr_pose_refiner_backward.argtypes = [C.c_int, C.c_int, C.c_int, fp, ll, ll, C.POINTER(fp), C.POINTER(fp), fp,
+                                              C.POINTER(fp), C.POINTER(fp), fp, vp]
+    lib.gsr_pose_refiner_forward.restype = lib.gsr_pose_refiner_backward.restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

@@ -32,6 +32,7 @@ SOURCES = [
     ("loss.hip", []),
     ("probe.hip", []),
     ("mlp.hip", []),
+    ("pose_refiner.hip", []),
     ("pbr.hip", []),
     ("bake.hip", ["-ffp-contract=off"]),
     ("pbr_loss.hip", []),

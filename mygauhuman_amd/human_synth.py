@@ -115,11 +115,16 @@ def view_camera(body, W, H, view, n_views=8, device="cuda", radius=2.4, fov_deg=
     return cam
 
 
-def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="affine", body="smpl"):
+def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="affine", body="smpl", pose_decoder="stand_in"):
     """(model, body arrays).  model.SMPL_NEUTRAL holds the body tables as device tensors; motion=True attaches the two decoders
     (decoder = "affine": the 3 x J stand-in; "reference_size": nets.FusedLBSOffsetDecoder -- the reference network's layers,
     random init -- on the fused kernels (at both J = 24 and 55); "reference_size_torch": the same module in torch ops).
-    body: "smpl" (default, 24 joints) or "smplx" (55 joints); V = None: the body's own vertex count."""
+    body: "smpl" (default, 24 joints) or "smplx" (55 joints); V = None: the body's own vertex count.  pose_decoder = "stand_in" (the
+    PoseRefiner above), "reference_size" (nets_pose.FusedBodyPoseRefiner as scene/gaussian_model.py:95 builds it -- width 128, depth 2,
+    the reference's initialisation under torch.manual_seed(seed + 5) -- on the fused kernels) or "reference_size_torch" (the same module
+    in torch ops)."""
+    if pose_decoder not in ("stand_in", "reference_size", "reference_size_torch"):
+        raise ValueError(f"human_synth.build: pose_decoder = {pose_decoder!r}")
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
     kind = body
     body = body_arrays(V, seed, kind)
@@ -129,7 +134,14 @@ def build(P, V=None, device="cuda", seed=0, motion=False, sh_degree=3, decoder="
     model = HumanGaussianModel.from_arrays(gaussian_arrays(body, P, seed), sh_degree, smpl=smpl, motion_offset_flag=motion,
                                            device=device, seed=seed)
     if motion:
-        model.pose_decoder = PoseRefiner(joints=nj).to(device)
+        if pose_decoder == "stand_in":
+            model.pose_decoder = PoseRefiner(joints=nj).to(device)
+        else:
+            from .nets_pose import FusedBodyPoseRefiner
+            torch.manual_seed(seed + 5)
+            ref = FusedBodyPoseRefiner(total_bones=nj, embedding_size=3 * (nj - 1), mlp_width=128, mlp_depth=2).to(device)
+            ref.use_fused = pose_decoder == "reference_size"
+            model.pose_decoder = ref
         if decoder in ("reference_size", "reference_size_torch"):
             from .nets import FusedLBSOffsetDecoder
             torch.manual_seed(seed + 7)
