@@ -1,12 +1,14 @@
 """`diff_gaussian_rasterization._C`: the three raw bindings of the reference extension (DGR/ext.cpp:15-19),
 same positional signatures and return tuples (DGR/rasterize_points.h:19-70), implemented over the C ABI of
 libgsr.so.  Torch only owns memory and the stream here; all compute is in the HIP library."""
+import contextlib
 import ctypes as C
 
 import torch
 
 from .. import _lib
 from .._lib import ALLOC_FN, check, lib, ptr
+from ..fastpath import DeferredStatus
 
 
 def _f32c(t, name):
@@ -45,21 +47,17 @@ class _Scratch:
             return 0
 
 
-FWD_ZERO_ROWS = 2   # GSR_FWD_ZERO_ROWS / GSR_BWD_ROWS_ZEROED (include/gsr.h): the forward zeroes the gradient rows, the backward
-BWD_ROWS_ZEROED = 2  # of the same frame then skips its fill kernel -- `rows_zeroed=True` on the three bindings below
-
-
-def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, extra=None, rows_zeroed=False):
-    """RasterizeGaussiansCUDA (DGR/rasterize_points.cu:36-120).
-
-    `extra` (extension): [P, 18] float32 feature channels blended in the same pass (fused multi-feature render); the
-    return tuple then carries a ninth element, out_extra [18, H, W]."""
+def _forward_inputs(name, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                    projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug, extra):
+    """What both forward bindings share: validation, the output images and, when P > 0, the float32 inputs and the arguments
+    around each entry point's own slots:  entry(<scratch>, *head, <num_rendered | status words>, *tail).
+    Returns ((color, depth, alpha, radii, out_extra | None), head, tail, inputs); head is None when P = 0 (nothing to launch:
+    the images are zero, out_extra holds the background).  `inputs` keeps the converted tensors that head / tail point into
+    alive: hold it until the call has returned."""
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
-        raise RuntimeError("rasterize_gaussians: tensors must live on a HIP device (no CPU path)")
+        raise RuntimeError(f"{name}: tensors must live on a HIP device (no CPU path)")
     dev = means3D.device
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     # the kernels write every pixel and every radius, so no fill kernels are needed unless nothing is launched
@@ -68,8 +66,6 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     out_depth = new((1, H, W), dtype=torch.float32, device=dev)
     out_alpha = new((1, H, W), dtype=torch.float32, device=dev)
     radii = new((P,), dtype=torch.int32, device=dev)
-    geom, binning, img = _Scratch(dev), _Scratch(dev), _Scratch(dev)
-    rendered = C.c_int(0)
     out_extra = None
     if extra is not None:
         if tuple(extra.shape) != (P, _lib.N_EXTRA):
@@ -78,28 +74,46 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         out_extra = new((_lib.N_EXTRA, H, W), dtype=torch.float32, device=dev)
         if P == 0:
             out_extra += background.to(dev).float().repeat(_lib.N_EXTRA // 3)[:, None, None]
-    if P != 0:
-        M = sh.size(1) if sh.numel() != 0 else 0
-        means3D, colors, opacity = _f32c(means3D, "means3D"), _f32c(colors, "colors"), _f32c(opacity, "opacity")
-        scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D")
-        (sh, sh_dtype), background = _sh(sh), _f32c(background, "background")
-        viewmatrix, projmatrix, campos = _f32c(viewmatrix, "viewmatrix"), _f32c(projmatrix, "projmatrix"), _f32c(campos, "campos")
+    images = (out_color, out_depth, out_alpha, radii, out_extra)
+    if P == 0:
+        return images, None, None, None
+    M = sh.size(1) if sh.numel() != 0 else 0
+    means3D, colors, opacity = _f32c(means3D, "means3D"), _f32c(colors, "colors"), _f32c(opacity, "opacity")
+    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D")
+    (sh, sh_dtype), background = _sh(sh), _f32c(background, "background")
+    viewmatrix, projmatrix, campos = _f32c(viewmatrix, "viewmatrix"), _f32c(projmatrix, "projmatrix"), _f32c(campos, "campos")
+    head = (P, int(degree), int(M), ptr(background), W, H, ptr(means3D), ptr(sh), ptr(colors), ptr(opacity), ptr(scales),
+            float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix), ptr(campos),
+            float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), out_color.data_ptr(), out_depth.data_ptr(),
+            out_alpha.data_ptr(), radii.data_ptr(), int(bool(debug)))
+    tail = (ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if out_extra is None else out_extra.data_ptr(), sh_dtype,
+            _stream(dev))
+    inputs = (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, extra)
+    return images, head, tail, inputs
+
+
+def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                        prefiltered, debug, extra=None):
+    """RasterizeGaussiansCUDA (DGR/rasterize_points.cu:36-120).
+
+    `extra` (extension): [P, 18] float32 feature channels blended in the same pass (fused multi-feature render); the
+    return tuple then carries a ninth element, out_extra [18, H, W]."""
+    (out_color, out_depth, out_alpha, radii, out_extra), head, tail, _inputs = _forward_inputs(
+        "rasterize_gaussians", background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug, extra)
+    dev = means3D.device
+    geom, binning, img = _Scratch(dev), _Scratch(dev), _Scratch(dev)
+    rendered = C.c_int(0)
+    if head is not None:
         with torch.cuda.device(dev):
-            rc = lib.gsr_rasterize_forward_ex(
-                geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), int(M), ptr(background), W, H,
-                ptr(means3D), ptr(sh), ptr(colors), ptr(opacity), ptr(scales), float(scale_modifier), ptr(rotations),
-                ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix), ptr(campos), float(tan_fovx), float(tan_fovy),
-                int(bool(prefiltered)), out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(),
-                radii.data_ptr(), int(bool(debug)) | (FWD_ZERO_ROWS if rows_zeroed else 0), C.byref(rendered), ptr(extra),
-                0 if extra is None else _lib.N_EXTRA,
-                None if out_extra is None else out_extra.data_ptr(), sh_dtype, _stream(dev))
+            rc = lib.gsr_rasterize_forward_ex(geom.cb, None, binning.cb, None, img.cb, None, *head, C.byref(rendered), *tail)
         for s in (geom, binning, img):
             if s.error is not None:
                 raise s.error
-        check(rc, "gsr_rasterize_forward")
-    if extra is not None:
-        return rendered.value, out_color, out_depth, out_alpha, radii, geom.tensor, binning.tensor, img.tensor, out_extra
-    return rendered.value, out_color, out_depth, out_alpha, radii, geom.tensor, binning.tensor, img.tensor
+        check(rc, "gsr_rasterize_forward_ex")
+    out = rendered.value, out_color, out_depth, out_alpha, radii, geom.tensor, binning.tensor, img.tensor
+    return out + (out_extra,) if extra is not None else out
 
 
 PREFILTER_MSG = "Point is filtered although prefiltered is set. This shouldn't happen!"  # CR/auxiliary.h:158
@@ -115,15 +129,14 @@ class AsyncCapacity:
 
     The blocking read of num_rendered (CR/rasterizer_impl.cu:283) exists to size the binning buffer.  On a 288 GB part the
     buffer is simply sized generously instead -- max(MIN, 64 instances per Gaussian, 2 x the largest R seen so far on that
-    device), 24 B per instance -- and the device reports R and a flag word into `status`.  The words travel to pinned host memory
-    with an asynchronous copy; they are examined when the frame's backward starts, at the next forward on that device, by
-    check(watch) -- which render() calls itself for frames that will have no backward -- or by check_all(): an overflow raises
-    RuntimeError there (the overflowing frame rendered only the background) and the capacity is raised for the retry.
-    All state is kept per device."""
+    device), 24 B per instance -- and the device writes R and a flag word into pinned host words (fastpath.DeferredStatus, one per
+    device).  They are examined when the frame's backward starts, at the next forward on that device, by check(watch) -- which
+    render() calls itself for frames that will have no backward -- or by check_all(): an overflow raises RuntimeError there (the
+    overflowing frame rendered only the background) and the capacity is raised for the retry."""
     MIN = 4 << 20
-    _state = {}  # device index -> dict(largest_R, pending, pinned)
+    _state = {}  # device index -> _DeviceWatches
     # status tensors of forwards that were recorded into a HIP graph (torch.cuda.graph): a captured region cannot hold the pinned
-    # copy / event of watch() (they would bake a host pointer and an unqueryable event into the graph), so those forwards are
+    # words / event of a watch (they would bake a host pointer and an unqueryable event into the graph), so those forwards are
     # checked by the caller after replays: AsyncCapacity.check_graph_status()
     graph_status = []
 
@@ -133,51 +146,17 @@ class AsyncCapacity:
         idx = torch.cuda.current_device() if idx is None else idx
         st = cls._state.get(idx)
         if st is None:
-            st = cls._state[idx] = dict(largest_R=0, pending=[], pinned=[])
+            st = cls._state[idx] = _DeviceWatches()
         return st
 
     @classmethod
     def capacity(cls, P, device=None):
-        return int(max(cls.MIN, 64 * P, 2 * cls._dev(device if device is not None else "cuda")["largest_R"]))
+        return int(max(cls.MIN, 64 * P, 2 * cls._dev(device if device is not None else "cuda").largest_R))
 
     @classmethod
     def status_words(cls, device):
-        """Two pinned host words for a forward's (R, flags): pinned memory is mapped into the device's address space, so the
-        binning kernel writes them straight to the host -- no device tensor, no copy kernel; the event of watch() tells the host
-        when they are there."""
-        st = cls._dev(device)
-        return st["pinned"].pop() if st["pinned"] else torch.zeros(2, dtype=torch.int32).pin_memory()
-
-    @classmethod
-    def watch(cls, host, capacity, device):
-        st = cls._dev(device)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(device))
-        w = [host, ev, int(capacity), False, st]
-        st["pending"].append(w)
-        return w
-
-    @classmethod
-    def _examine(cls, w, wait):
-        if w is None or w[3]:
-            return
-        if wait:
-            w[1].synchronize()
-        elif not w[1].query():
-            return
-        w[3] = True
-        st = w[4]
-        if w in st["pending"]:
-            st["pending"].remove(w)
-        R, flags = int(w[0][0]) & 0xFFFFFFFF, int(w[0][1])
-        st["pinned"].append(w[0])
-        st["largest_R"] = max(st["largest_R"], R)
-        if flags & 2:
-            raise RuntimeError("rasterize_gaussians_async: " + PREFILTER_MSG)
-        if flags & 1:
-            raise BinningCapacityExceeded(
-                f"rasterize_gaussians_async: {R} (Gaussian, tile) instances exceeded the binning capacity of {w[2]}; "
-                "that frame rendered only the background.  The capacity has been raised: render it again.")
+        """Two pinned host words for a forward's (R, flags): the binning kernel writes them straight to the host."""
+        return cls._dev(device).words()
 
     KEEP_IN_FLIGHT = 2  # frames whose flag words may still be unread when the next forward is issued
 
@@ -186,27 +165,23 @@ class AsyncCapacity:
         """Examine what has arrived without blocking, and BLOCK on watches more than KEEP_IN_FLIGHT frames old (their events
         fired long ago, so this costs nothing): at most the last KEEP_IN_FLIGHT frames of a loop can be unverified --
         check_all() / `with AsyncCapacity.frames():` closes that window."""
-        pending = list(cls._dev(device if device is not None else "cuda")["pending"])
-        for k, w in enumerate(pending):
-            cls._examine(w, wait=k < len(pending) - cls.KEEP_IN_FLIGHT)
+        st = cls._dev(device if device is not None else "cuda")
+        st.examine(block_older_than=st.issued - 1 - cls.KEEP_IN_FLIGHT, nonblocking=True)
 
     @classmethod
+    @contextlib.contextmanager
     def frames(cls):
         """Context manager for forward-only loops over the sync-free rasterizer: every frame issued inside is verified when the
         block ends (raises for a frame that overflowed)."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def _cm():
-            try:
-                yield cls
-            finally:
-                cls.check_all()
-        return _cm()
+        try:
+            yield cls
+        finally:
+            cls.check_all()
 
     @classmethod
-    def check(cls, w):
-        cls._examine(w, wait=True)
+    def check(cls, watch):
+        for st in cls._state.values():   # (only the device that issued the watch holds it)
+            st.check(watch)
 
     @classmethod
     def check_graph_status(cls):
@@ -223,67 +198,67 @@ class AsyncCapacity:
     @classmethod
     def check_all(cls):
         for st in list(cls._state.values()):
-            for w in list(st["pending"]):
-                cls._examine(w, wait=True)
+            st.check_all()
+
+
+class _DeviceWatches(DeferredStatus):
+    """AsyncCapacity's state of one device: the pending (R, flags) words of its forwards, tagged with their capacity, and the
+    largest R seen."""
+
+    def __init__(self):
+        super().__init__(2, self._decide)
+        self.largest_R = 0
+
+    def __getitem__(self, key):
+        """AsyncCapacity._dev(device)['largest_R' | 'pending']: the per-device state also reads as the mapping it was."""
+        if key not in ("largest_R", "pending"):
+            raise KeyError(key)
+        return getattr(self, key)
+
+    def _decide(self, watch, words):
+        R, flags = words[0] & 0xFFFFFFFF, words[1]
+        self.largest_R = max(self.largest_R, R)
+        if flags & 2:
+            raise RuntimeError("rasterize_gaussians_async: " + PREFILTER_MSG)
+        if flags & 1:
+            raise BinningCapacityExceeded(
+                f"rasterize_gaussians_async: {R} (Gaussian, tile) instances exceeded the binning capacity of {watch.tag}; "
+                "that frame rendered only the background.  The capacity has been raised: render it again.")
 
 
 def rasterize_gaussians_async(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                               projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                              debug, extra=None, capacity=None, rows_zeroed=False):
+                              debug, extra=None, capacity=None):
     """Sync-free forward (extension): same inputs as rasterize_gaussians, no host read of num_rendered.
     Returns (capacity, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer, out_extra | None, watch) where
     `capacity` takes the place of num_rendered in rasterize_gaussians_backward and `watch` is the deferred overflow check
     (AsyncCapacity.check(watch))."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if not means3D.is_cuda:
-        raise RuntimeError("rasterize_gaussians_async: tensors must live on a HIP device (no CPU path)")
+    (out_color, out_depth, out_alpha, radii, out_extra), head, tail, _inputs = _forward_inputs(
+        "rasterize_gaussians_async", background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug, extra)
     dev = means3D.device
     P, H, W = means3D.size(0), int(image_height), int(image_width)
-    if P == 0:
-        out = rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-                                  projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
-                                  debug, extra=extra, rows_zeroed=rows_zeroed)
-        return (0,) + tuple(out[1:8]) + ((out[8] if extra is not None else None), None)
+    u8 = torch.uint8
+    if head is None:
+        e = [torch.empty(0, dtype=u8, device=dev) for _ in range(3)]
+        return (0, out_color, out_depth, out_alpha, radii, *e, out_extra, None)
     capturing = torch.cuda.is_current_stream_capturing()
     if not capturing:
         AsyncCapacity.poll(dev)
     cap = int(capacity) if capacity is not None else AsyncCapacity.capacity(P, dev)
-    f32, u8 = torch.float32, torch.uint8
-    out_color = torch.empty((3, H, W), dtype=f32, device=dev)
-    out_depth = torch.empty((1, H, W), dtype=f32, device=dev)
-    out_alpha = torch.empty((1, H, W), dtype=f32, device=dev)
-    radii = torch.empty((P,), dtype=torch.int32, device=dev)
     geom = torch.empty((lib.gsr_geometry_bytes(P),), dtype=u8, device=dev)
     img = torch.empty((lib.gsr_image_bytes(W, H),), dtype=u8, device=dev)
     binning = torch.empty((lib.gsr_binning_bytes(cap, W, H),), dtype=u8, device=dev)
     # the (R, flags) words: a device tensor inside a graph capture (examined after replays), pinned host words otherwise
     status = torch.empty((2,), dtype=torch.int32, device=dev) if capturing else AsyncCapacity.status_words(dev)
-    out_extra = None
-    if extra is not None:
-        if tuple(extra.shape) != (P, _lib.N_EXTRA):
-            raise RuntimeError(f"extra must have shape (num_points, {_lib.N_EXTRA})")
-        extra = _f32c(extra, "extra")
-        out_extra = torch.empty((_lib.N_EXTRA, H, W), dtype=f32, device=dev)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    means3D, colors, opacity = _f32c(means3D, "means3D"), _f32c(colors, "colors"), _f32c(opacity, "opacity")
-    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D")
-    (sh, sh_dtype), background = _sh(sh), _f32c(background, "background")
-    viewmatrix, projmatrix, campos = _f32c(viewmatrix, "viewmatrix"), _f32c(projmatrix, "projmatrix"), _f32c(campos, "campos")
     with torch.cuda.device(dev):
-        rc = lib.gsr_rasterize_forward_async_ex(
-            geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), P, int(degree), int(M), ptr(background), W, H, ptr(means3D),
-            ptr(sh), ptr(colors), ptr(opacity), ptr(scales), float(scale_modifier), ptr(rotations), ptr(cov3D_precomp),
-            ptr(viewmatrix), ptr(projmatrix), ptr(campos), float(tan_fovx), float(tan_fovy), int(bool(prefiltered)),
-            out_color.data_ptr(), out_depth.data_ptr(), out_alpha.data_ptr(), radii.data_ptr(),
-            int(bool(debug)) | (FWD_ZERO_ROWS if rows_zeroed else 0), status.data_ptr(), ptr(extra), 0 if extra is None else _lib.N_EXTRA,
-            None if out_extra is None else out_extra.data_ptr(), sh_dtype, _stream(dev))
-        check(rc, "gsr_rasterize_forward_async")
-        if capturing:
-            watch = None
-            AsyncCapacity.graph_status.append(status)
-        else:
-            watch = AsyncCapacity.watch(status, cap, dev)
+        check(lib.gsr_rasterize_forward_async_ex(geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), *head, status.data_ptr(),
+                                                 *tail), "gsr_rasterize_forward_async_ex")
+    watch = None
+    if capturing:
+        AsyncCapacity.graph_status.append(status)
+    else:
+        watch = AsyncCapacity._dev(dev).push(status, torch.cuda.current_stream(dev), tag=cap)
     return cap, out_color, out_depth, out_alpha, radii, geom, binning, img, out_extra, watch
 
 
@@ -336,7 +311,7 @@ def phase1_loss_forward(spec, color, alpha, out_extra):
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                  dL_dout_alpha, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, alphas,
-                                 debug, out=None, extra=None, dL_dout_extra=None, rows_zeroed=False, phase1=None):
+                                 debug, out=None, extra=None, dL_dout_extra=None, phase1=None):
     """RasterizeGaussiansBackwardCUDA (DGR/rasterize_points.cu:122-207).
 
     `out` (extension, keyword only in practice): dict name -> preallocated contiguous float32 tensor for any of
@@ -390,6 +365,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         dL_dout_color, dL_dout_depth = opt(dL_dout_color, "dL_dout_color"), opt(dL_dout_depth, "dL_dout_depth")
         dL_dout_alpha = opt(dL_dout_alpha, "dL_dout_alpha")
         radii = radii.contiguous()
+        # (GSR_FWD_ZERO_ROWS / GSR_BWD_ROWS_ZEROED -- the forward zeroing the gradient rows so that the backward needs no fill
+        # kernel -- measured SLOWER in the render() frame: preprocess forward 9.7 -> 19.2 us and backward 18.2 -> 28.7 us against
+        # one 5 us fill kernel; the bindings leave both flags off)
+        entry, name, loss = lib.gsr_rasterize_backward_ex, "gsr_rasterize_backward_ex", ()
         if phase1 is not None:
             # phase1 = (Phase1Loss, stats [8], upstream dL/dloss (0-dim tensor or None), color [3,H,W], out_extra [18,H,W])
             spec, stats, upstream, p1_color, p1_extra = phase1
@@ -397,22 +376,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 raise RuntimeError("the fused phase-1 loss needs the fused multi-feature pass (extra colours)")
             up = None if upstream is None else upstream.detach().to(torch.float32).reshape(1).contiguous()
             st = spec.struct(_f32c(p1_color, "color"), alphas, _f32c(p1_extra, "out_extra"), stats, up)
-            with torch.cuda.device(dev):
-                rc = lib.gsr_rasterize_backward_phase1_loss(
-                    P, int(degree), int(M), int(R), ptr(background), W, H, ptr(means3D), ptr(sh), ptr(colors), ptr(alphas),
-                    ptr(scales), float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix),
-                    ptr(campos), float(tan_fovx), float(tan_fovy), ptr(radii), geomBuffer.data_ptr(),
-                    binningBuffer.data_ptr(), imageBuffer.data_ptr(), ptr(dL_dout_color), ptr(dL_dout_depth),
-                    ptr(dL_dout_alpha), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
-                    dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-                    dL_dsh.data_ptr() if M else None, None if dL_dscales is None else dL_dscales.data_ptr(),
-                    None if dL_drotations is None else dL_drotations.data_ptr(),
-                    int(bool(debug)) | (BWD_ROWS_ZEROED if rows_zeroed else 0), ptr(extra), _lib.N_EXTRA, extra_ptrs,
-                    dL_dextra.data_ptr(), sh_dtype, C.byref(st), _stream(dev))
-            check(rc, "gsr_rasterize_backward_phase1_loss")
-            return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dextra
+            entry, name, loss = lib.gsr_rasterize_backward_phase1_loss, "gsr_rasterize_backward_phase1_loss", (C.byref(st),)
         with torch.cuda.device(dev):
-            rc = lib.gsr_rasterize_backward_ex(
+            rc = entry(
                 P, int(degree), int(M), int(R), ptr(background), W, H, ptr(means3D), ptr(sh), ptr(colors), ptr(alphas),
                 ptr(scales), float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix),
                 ptr(campos), float(tan_fovx), float(tan_fovy), ptr(radii), geomBuffer.data_ptr(),
@@ -420,10 +386,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 ptr(dL_dout_alpha), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
                 dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
                 dL_dsh.data_ptr() if M else None, None if dL_dscales is None else dL_dscales.data_ptr(),
-                None if dL_drotations is None else dL_drotations.data_ptr(), int(bool(debug)) | (BWD_ROWS_ZEROED if rows_zeroed else 0),
+                None if dL_drotations is None else dL_drotations.data_ptr(), int(bool(debug)),
                 ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if extra is None else extra_ptrs,
-                None if dL_dextra is None else dL_dextra.data_ptr(), sh_dtype, _stream(dev))
-        check(rc, "gsr_rasterize_backward")
+                None if dL_dextra is None else dL_dextra.data_ptr(), sh_dtype, *loss, _stream(dev))
+        check(rc, name)
     if extra is not None:
         return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dextra
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations

@@ -71,14 +71,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
-        # (GSR_FWD_ZERO_ROWS -- the forward preprocess zeroing the gradient rows so that the backward needs no fill kernel -- is
-        # built and measured SLOWER in the render() frame: preprocess forward 9.7 -> 19.2 us and backward 18.2 -> 28.7 us (it then
-        # clears the rows it consumed) against one 5 us fill kernel; the wrappers do not use it)
-        ctx.rows_zeroed = False
         ctx.watch = None
         if sync_free:
-            out = _call_guarded(lambda *x: _C.rasterize_gaussians_async(*x, rows_zeroed=ctx.rows_zeroed), args, rs.debug,
-                                "snapshot_fw.dump", "forward")
+            out = _call_guarded(_C.rasterize_gaussians_async, args, rs.debug, "snapshot_fw.dump", "forward")
             num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer = out[:8]
             if will_backward:
                 ctx.watch = out[9]   # examined at the end of backward(), before an optimizer can consume the gradients
@@ -86,7 +81,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _C.AsyncCapacity.check(out[9])   # a frame nobody will backpropagate through: raise on THIS call
         else:
             num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer = _call_guarded(
-                lambda *x: _C.rasterize_gaussians(*x, rows_zeroed=ctx.rows_zeroed), args, rs.debug, "snapshot_fw.dump", "forward")
+                _C.rasterize_gaussians, args, rs.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
@@ -105,8 +100,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, grad_alpha, sh,
                 rs.sh_degree, rs.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, alpha, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_guarded(lambda *x: _C.rasterize_gaussians_backward(*x, rows_zeroed=ctx.rows_zeroed), args, rs.debug,
-                                         "snapshot_bw.dump", "backward")
+         grad_rotations) = _call_guarded(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", "backward")
         if ctx.watch is not None:   # the whole backward is queued: wait for the FORWARD's overflow flag only
             _C.AsyncCapacity.check(ctx.watch)
         # gradients in the order of forward()'s inputs (:146-156); raster_settings gets None
@@ -165,7 +159,6 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
                 _C.AsyncCapacity.check(watch)
         else:
             out = _C.rasterize_gaussians(*args, extra=extra)
-        ctx.rows_zeroed = False
         num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer, out_extra = out
         ctx.set_materialize_grads(False)  # untouched images arrive as None in backward, not as zero tensors
         # (gradlink) render(): the attribute kernel of this frame consumes the same positions and its backward runs after this one
@@ -210,7 +203,7 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos,
             geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, alpha, rs.debug, out={"lean": True}, extra=extra,
-            dL_dout_extra=list(grad_feats), rows_zeroed=ctx.rows_zeroed, phase1=phase1)
+            dL_dout_extra=list(grad_feats), phase1=phase1)
         if ctx.watch is not None:
             # the whole backward is queued; wait for the FORWARD's overflow flag only (the GPU stays busy with the backward)
             # so that an overflow raises before the optimizer consumes these gradients

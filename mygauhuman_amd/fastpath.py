@@ -6,12 +6,77 @@ all of that memory for a fixed problem shape and drives gsr_rasterize_forward_as
 gsr_alpha_mask_loss_backward directly: no host<->device synchronisation, no allocations and no fill kernels inside
 a step, so the host can run ahead of the GPU.  The binning buffer is sized for `capacity` instances; the device
 reports R and an overflow flag in `status` (checked with .overflowed(), which does synchronise).
+
+DeferredStatus is how the sync-free paths (_C.AsyncCapacity, parallel.ViewParallelStep / ViewParallelRender) read such status
+words later without stalling the host.
 """
+import dataclasses
+
 import torch
 
 from ._lib import SH_F16, SH_F32, check, lib
 
 ROWS_ZEROED = 2  # GSR_BWD_ROWS_ZEROED (include/gsr.h)
+
+
+@dataclasses.dataclass(eq=False)   # identity comparison: an entry is looked up in the FIFO by itself, never by its tensors
+class Deferred:
+    index: int            # issue order within its DeferredStatus, from 0
+    tag: object           # whatever the decision needs besides the words (AsyncCapacity: the binning capacity)
+    words: torch.Tensor   # pinned int32 host words the device writes
+    event: torch.cuda.Event
+
+
+class DeferredStatus:
+    """Status words that the device writes and the host examines later, oldest first, never silently.
+
+    words() hands out a pinned int32 host buffer of `n_words`: pinned memory is mapped into the device's address space, so a kernel
+    writes the words straight to the host (no copy).  push() records an event behind the work that writes them and queues the
+    entry.  examine() waits for every entry with index <= block_older_than and, when nonblocking, also takes later ones whose event
+    has already fired; for each one the words are read, the buffer and the event go back to their pools, and only then is
+    decide(entry, words) called -- which raises for a bad entry.  Once warmed up, nothing is allocated."""
+
+    def __init__(self, n_words, decide):
+        self.n_words, self.decide = int(n_words), decide
+        self.issued = 0
+        self.pending = []
+        self._words, self._events = [], []
+
+    def words(self):
+        return self._words.pop() if self._words else torch.zeros(self.n_words, dtype=torch.int32).pin_memory()
+
+    def push(self, words, stream, tag=None):
+        """Queue `words` behind the work issued so far on `stream`; returns the entry."""
+        ev = self._events.pop() if self._events else torch.cuda.Event()
+        ev.record(stream)
+        entry = Deferred(self.issued, tag, words, ev)
+        self.issued += 1
+        self.pending.append(entry)
+        return entry
+
+    def examine(self, block_older_than=-1, nonblocking=False):
+        for e in list(self.pending):
+            if e.index <= block_older_than:
+                e.event.synchronize()
+            elif not (nonblocking and e.event.query()):
+                continue
+            self._retire(e)
+
+    def check(self, entry):
+        """Wait for one entry and decide on it; an entry examined already is left alone."""
+        if entry in self.pending:
+            entry.event.synchronize()
+            self._retire(entry)
+
+    def check_all(self):
+        self.examine(block_older_than=self.issued)
+
+    def _retire(self, e):
+        self.pending.remove(e)
+        words = e.words.tolist()
+        self._words.append(e.words)
+        self._events.append(e.event)
+        self.decide(e, words)
 
 
 class RasterSession:
@@ -72,7 +137,7 @@ class RasterSession:
             p["scales"].data_ptr(), float(scale_modifier), p["rotations"].data_ptr(), None, cam["viewmatrix"].data_ptr(),
             cam["projmatrix"].data_ptr(), cam["campos"].data_ptr(), float(cam["tanfovx"]), float(cam["tanfovy"]), 0,
             self.color.data_ptr(), self.depth.data_ptr(), self.alpha.data_ptr(), self.radii.data_ptr(), 0,
-            self.status.data_ptr(), None, 0, None, sh_dtype, self._stream()), "gsr_rasterize_forward_async")
+            self.status.data_ptr(), None, 0, None, sh_dtype, self._stream()), "gsr_rasterize_forward_async_ex")
         return self.color, self.depth, self.alpha, self.radii
 
     def alpha_mask_loss_backward(self, gt, mask, lambda_alpha=0.1):
@@ -94,7 +159,7 @@ class RasterSession:
             dL_dalpha.data_ptr(), self.dL_dmean2D.data_ptr(), self.dL_dconic.data_ptr(), out["opacity"].data_ptr(),
             self.dL_dcolors.data_ptr(), out["means3D"].data_ptr(), self.dL_dcov3D.data_ptr(), out["sh"].data_ptr(),
             out["scales"].data_ptr(), out["rotations"].data_ptr(), ROWS_ZEROED, None, 0, None, None, sh_dtype, self._stream()),
-            "gsr_rasterize_backward")
+            "gsr_rasterize_backward_ex")
 
     def backward_alpha_mask_loss(self, params, cam, bg, sh_degree, gt, mask, lambda_alpha, out, scale_modifier=1.0):
         """backward() of the loss  mean|color - gt| + lambda_alpha * mean (alpha - mask)^2  of the last forward, with the loss

@@ -9,9 +9,10 @@ What changes underneath:
     seven images come out of ONE fused pass (one preprocess + binning, a 21-channel blend, one backward) with the same
     outputs and gradients; `pipe.separate_feature_passes = True` restores the seven separate calls;
   * no per-frame host read of num_rendered (CR/rasterizer_impl.cu:283): the fused pass runs through the sync-free entry with a
-    generous binning capacity and a deferred, never-silent overflow check (diff_gaussian_rasterization._C.AsyncCapacity: examined
-    when the frame's backward runs, at later frames, and by AsyncCapacity.check_all() / `with AsyncCapacity.frames():` for
-    forward-only loops); `pipe.sync_free_raster = False` restores the reference's blocking read.
+    generous binning capacity and a deferred, never-silent overflow check (diff_gaussian_rasterization._C.AsyncCapacity: the
+    device writes (R, flags) into pinned host words, a fastpath.DeferredStatus per device, examined when the frame's backward
+    runs, at later frames, and by AsyncCapacity.check_all() / `with AsyncCapacity.frames():` for forward-only loops);
+    `pipe.sync_free_raster = False` restores the reference's blocking read.
 `pc` is any object exposing the reference GaussianModel accessors (scene_model.HumanGaussianModel or the reference's own
 class); `viewpoint_camera` exposes FoVx, FoVy, image_height, image_width, world_view_transform, full_proj_transform,
 camera_center, smpl_param, big_pose_smpl_param, big_pose_world_vertex (scene/cameras.py:17-74) and optionally

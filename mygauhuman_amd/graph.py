@@ -12,8 +12,9 @@ resolved per stream), so the whole step can be recorded once and replayed with O
 Rules of a captured region (violations bake a stale pointer or an unqueryable object into the graph):
   * per-frame inputs are device tensors updated IN PLACE (camera matrices, SMPL pose, ground truth); image size and field of
     view are by-value kernel arguments: one GraphedFrame per camera intrinsics;
-  * no pinned device-to-host copies / event records: rasterize_gaussians_async notices the capture and leaves its deferred
-    overflow watch out (AsyncCapacity.graph_status keeps the status tensors for check());
+  * no pinned status words / event records (fastpath.DeferredStatus): rasterize_gaussians_async notices the capture, writes its
+    (R, flags) into a device tensor and leaves its deferred overflow watch out (AsyncCapacity.graph_status keeps those tensors
+    for check());
   * the number of Gaussians is baked in: capture again after a densification / pruning step;
   * stage profiling (gsr_profile_enable) must be off;
   * ROCm 7.2: under the HIP runtime's graph packet capture (the default) a memset NODE on memory of the graph's pool replays wrong

@@ -14,7 +14,7 @@ Densification statistics use a second, tiny bucket (sum of gradient norms + visi
 scene/gaussian_model.py:764-766, train.py:403).
 """
 import os
-from collections import OrderedDict, deque
+from collections import OrderedDict
 
 import torch
 import torch.distributed as dist
@@ -368,13 +368,14 @@ class ViewParallelStep:
       * the session's overflow flag rides in one slot of the all-reduced bucket, so after the reduction every rank holds the
         number of ranks that overflowed; the gradients of such a step are multiplied by zero ON THE DEVICE on every rank
         (a consistent skipped step) instead of averaging a blank view into the mean;
-      * (ranks overflowed, R, own flag) are written into pinned host memory by the same one-thread bookkeeping kernel that
-        forms the scale (gsr_step_status) and are examined once the step is `max_in_flight` calls old (by then its event has
-        long fired: the host does not stall) and by check(): an overflowed step raises BinningOverflow there -- at the same
-        call on every rank, so the collectives stay matched -- after this rank's session has been regrown to 2 x its R."""
+      * (ranks overflowed, R, own flag) are written into pinned host memory (fastpath.DeferredStatus) by the same one-thread
+        bookkeeping kernel that forms the scale (gsr_step_finish) and are examined once the step is `max_in_flight` calls old
+        (by then its event has long fired: the host does not stall) and by check(): an overflowed step raises BinningOverflow
+        there -- at the same call on every rank, so the collectives stay matched -- after this rank's session has been regrown
+        to 2 x its R."""
 
     def __init__(self, params, sh_degree, cam, bg, group=None, slack=1.3, compact_sh=None, max_in_flight=2, capacity=None):
-        from .fastpath import RasterSession
+        from .fastpath import DeferredStatus, RasterSession
         self.p = params  # dict: means3D, shs, opacities, scales, rotations (device tensors)
         self.deg = sh_degree
         self.group = group
@@ -395,9 +396,8 @@ class ViewParallelStep:
         else:
             self.session = RasterSession(P, cam["W"], cam["H"], M, dev, capacity)
         self.max_in_flight = int(max_in_flight)
-        self.steps = 0
-        self.pending = deque()   # (step index, pinned uint32 [ranks overflowed, R, own flag], event)
-        self._pinned, self._events = [], []
+        # one entry per step (entry index = step index): [ranks overflowed, R, own flag], or the forward's [R, flags] if world == 1
+        self.reports = DeferredStatus(3, self._decide)
         self._scale = torch.zeros(1, dtype=torch.float32, device=dev)
         self.timer = ExchangeTimer()      # the whole exchange as the compute stream sees it (all-reduce + waiting for the all-gather)
         self.ar_timer = ExchangeTimer()   # the all-reduce alone; the all-gather times itself on its side stream (compact.allgather_ms)
@@ -416,44 +416,32 @@ class ViewParallelStep:
                                   self._scale.data_ptr(), None if report is None else report.data_ptr(),
                                   torch.cuda.current_stream(dev).cuda_stream), "gsr_step_status")
 
-    def _report_buffer(self):
-        # pinned host memory is mapped into the device's address space: the bookkeeping kernel writes the three words
-        # straight into it (no copy engine involved), the event tells the host when they are there
-        return self._pinned.pop() if self._pinned else torch.zeros(3, dtype=torch.int32).pin_memory()
-
-    def _examine(self, block_older_than):
-        while self.pending:
-            step, host, ev = self.pending[0]
-            if step > block_older_than:  # (never by ev.query(): ranks must raise at the same call)
-                return
-            ev.synchronize()
-            self.pending.popleft()
-            self._events.append(ev)
-            if self.world > 1:   # [ranks that overflowed, R, own flag], written by gsr_step_status after the all-reduce
-                ranks, R, own = int(host[0]), int(host[1]) & 0xFFFFFFFF, int(host[2]) != 0
-            else:                # the forward's own status words [R, flags], written straight into this pinned buffer
-                R, own = int(host[0]) & 0xFFFFFFFF, (int(host[1]) & 1) != 0
-                ranks = int(own)
-            self._pinned.append(host)
-            if ranks > 0:
-                old = self.session.capacity
-                if own:  # regrow this rank's buffers; queued kernels keep the old ones alive (stream-ordered allocator)
-                    self.session = self.session.regrown(2 * R + 4096)
-                raise BinningOverflow(
-                    f"step {step}: {ranks} rank(s) exceeded their binning capacity"
-                    + (f" (this rank: R = {R} > {old}; capacity raised to {self.session.capacity})" if own else "")
-                    + "; the step's gradients were zeroed on every rank -- repeat it")
+    def _decide(self, step, words):
+        if self.world > 1:   # [ranks that overflowed, R, own flag], written by gsr_step_finish after the all-reduce
+            ranks, R, own = words[0], words[1] & 0xFFFFFFFF, words[2] != 0
+        else:                # the forward's own status words [R, flags], written straight into this pinned buffer
+            R, own = words[0] & 0xFFFFFFFF, (words[1] & 1) != 0
+            ranks = int(own)
+        if ranks > 0:
+            old = self.session.capacity
+            if own:  # regrow this rank's buffers; queued kernels keep the old ones alive (stream-ordered allocator)
+                self.session = self.session.regrown(2 * R + 4096)
+            raise BinningOverflow(
+                f"step {step.index}: {ranks} rank(s) exceeded their binning capacity"
+                + (f" (this rank: R = {R} > {old}; capacity raised to {self.session.capacity})" if own else "")
+                + "; the step's gradients were zeroed on every rank -- repeat it")
 
     def check(self):
         """Block until every issued step has been examined (raises BinningOverflow for an overflowed one)."""
-        self._examine(block_older_than=self.steps)
+        self.reports.check_all()
 
     def __call__(self, cam, bg, gt, mask, reduce=True):
         """Returns (color, alpha, radii); afterwards self.grads[name] holds the (mean over ranks, if reduce) gradients."""
-        self._examine(block_older_than=self.steps - self.max_in_flight)
+        # by step index, never by event.query(): every rank must raise at the same call
+        self.reports.examine(block_older_than=self.reports.issued - self.max_in_flight)
         s, b = self.session, self.bucket
         dev = self._scale.device
-        host = self._report_buffer()
+        host = self.reports.words()
         if self.world == 1:
             # single process: the forward writes its status words (R, flags) straight into this step's pinned buffer (device-
             # mapped host memory) -- no bookkeeping kernel, no copy; the event below tells the host when they are there
@@ -489,10 +477,7 @@ class ViewParallelStep:
             if reduce and self.compact is not None:
                 self.compact.reconstruct(self.p["means3D"], self.deg, self._scale)
         # (a single process needs no scaling: its own overflowed step has exactly zero gradients already)
-        ev = self._events.pop() if self._events else torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self._scale.device))
-        self.steps += 1
-        self.pending.append((self.steps - 1, host, ev))
+        self.reports.push(host, torch.cuda.current_stream(dev))
         return s.color, s.alpha, s.radii
 
 
@@ -553,23 +538,13 @@ class ViewParallelRender:
     MODEL_LEAVES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "_normal", "_albedo", "_roughness")
 
     def __init__(self, model, pipe, bg, group=None, compact_sh=None, max_in_flight=2):
+        from .fastpath import DeferredStatus
         self.model, self.pipe, self.bg, self.group = model, pipe, bg, group
         dev = model.get_xyz.device
         self.device = dev
         self.world = world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
         self.P = P = int(model.get_xyz.shape[0])
-        leaves = OrderedDict()
-        for n in self.MODEL_LEAVES:
-            t = getattr(model, n, None)
-            if isinstance(t, torch.Tensor) and t.numel() and t.requires_grad:
-                leaves[n] = t
-        for mod_name in ("pose_decoder", "lweight_offset_decoder"):
-            mod = getattr(model, mod_name, None)
-            if isinstance(mod, torch.nn.Module):
-                for n, p_ in mod.named_parameters():
-                    if p_.requires_grad:
-                        leaves[f"{mod_name}.{n}"] = p_
-        self.leaves = leaves
+        self.leaves = leaves = self._model_leaves()
         dc, rest = leaves.get("_features_dc"), leaves.get("_features_rest")
         can_compact = (dc is not None and rest is not None and tuple(dc.shape) == (P, 1, 3) and tuple(rest.shape) == (P, 15, 3)
                        and getattr(pipe, "convert_SHs_python", False) and not getattr(pipe, "separate_feature_passes", False))
@@ -585,9 +560,7 @@ class ViewParallelRender:
         self._bucket_leaves = [n for n in shapes if n in leaves]
         self.max_radii = torch.zeros((P,), dtype=torch.int32, device=dev)
         self.max_in_flight = int(max_in_flight)
-        self.steps = 0
-        self.pending = deque()
-        self._pinned, self._events = [], []
+        self.reports = DeferredStatus(3, self._decide)   # one entry per step: [ranks overflowed, R, own flag]
         self._scale = torch.zeros(1, dtype=torch.float32, device=dev)
         self.timer = ExchangeTimer()      # the whole exchange as the compute stream sees it (all-reduce + waiting for the all-gather)
         self.ar_timer = ExchangeTimer()   # the all-reduce alone; the all-gather times itself on its side stream (compact.allgather_ms)
@@ -615,36 +588,29 @@ class ViewParallelRender:
         m.denom += self.stat_visible
         m.max_radii2D = torch.maximum(m.max_radii2D, self.max_radii.to(m.max_radii2D.dtype))
 
-    def _examine(self, block_older_than):
-        while self.pending:
-            step, host, ev = self.pending[0]
-            if step > block_older_than:
-                return
-            ev.synchronize()
-            self.pending.popleft()
-            self._events.append(ev)
-            ranks = int(host[0])
-            self._pinned.append(host)
-            if ranks > 0:
-                raise BinningOverflow(f"step {step}: {ranks} rank(s) exceeded their binning capacity; the step's gradients were "
-                                      "zeroed on every rank (the capacity of the overflowing rank has been raised) -- repeat it")
+    def _decide(self, step, words):
+        ranks = words[0]
+        if ranks > 0:
+            raise BinningOverflow(f"step {step.index}: {ranks} rank(s) exceeded their binning capacity; the step's gradients were "
+                                  "zeroed on every rank (the capacity of the overflowing rank has been raised) -- repeat it")
 
     def check(self):
-        self._examine(block_older_than=self.steps)
+        self.reports.check_all()
 
-    def _current_leaves(self):
-        cur = OrderedDict()
+    def _model_leaves(self):
+        """The model's trainable leaves by name: MODEL_LEAVES, then the parameters of its two networks."""
+        leaves = OrderedDict()
         for n in self.MODEL_LEAVES:
             t = getattr(self.model, n, None)
             if isinstance(t, torch.Tensor) and t.numel() and t.requires_grad:
-                cur[n] = t
+                leaves[n] = t
         for mod_name in ("pose_decoder", "lweight_offset_decoder"):
             mod = getattr(self.model, mod_name, None)
             if isinstance(mod, torch.nn.Module):
                 for n, p_ in mod.named_parameters():
                     if p_.requires_grad:
-                        cur[f"{mod_name}.{n}"] = p_
-        return cur
+                        leaves[f"{mod_name}.{n}"] = p_
+        return leaves
 
     def _rebind_leaves(self):
         """The model may REPLACE a leaf between two steps without changing its shape -- densify.reset_opacity (train.py:412) installs
@@ -654,7 +620,7 @@ class ViewParallelRender:
         model's leaves with the ones this object is bound to: same names and shapes -> the new tensors are adopted (the bucket is
         sized by shapes, nothing else changes); anything else -- densify / prune changed P, a leaf appeared or vanished -- raises and
         asks for a new ViewParallelRender, whose bucket is sized for the new model."""
-        cur = self._current_leaves()
+        cur = self._model_leaves()
         if int(self.model.get_xyz.shape[0]) != self.P or list(cur) != list(self.leaves) or any(
                 tuple(cur[n].shape) != tuple(self.leaves[n].shape) for n in cur):
             raise RuntimeError(
@@ -670,7 +636,7 @@ class ViewParallelRender:
         from . import attributes
         from .diff_gaussian_rasterization import _C as _RasterC
         from .gaussian_renderer import render
-        self._examine(block_older_than=self.steps - self.max_in_flight)
+        self.reports.examine(block_older_than=self.reports.issued - self.max_in_flight)   # by step index, like ViewParallelStep
         self._rebind_leaves()
         dev, b = self.device, self.bucket
         for t in self.leaves.values():
@@ -720,7 +686,7 @@ class ViewParallelRender:
                     self.compact.pack_posed(colors, g_colors, means_view, camera.camera_center, out["radii"])
             else:
                 self.max_radii.copy_(out["radii"])
-        host = self._pinned.pop() if self._pinned else torch.zeros(3, dtype=torch.int32).pin_memory()
+        host = self.reports.words()
         # ---- the exchange
         n_views = self.world if (self.world > 1 and reduce) else 1
         if n_views > 1:
@@ -759,8 +725,5 @@ class ViewParallelRender:
                 t.grad = self.compact.grad_rest
             else:
                 t.grad = b[n]
-        ev = self._events.pop() if self._events else torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))
-        self.steps += 1
-        self.pending.append((self.steps - 1, host, ev))
+        self.reports.push(host, torch.cuda.current_stream(dev))
         return out, loss
