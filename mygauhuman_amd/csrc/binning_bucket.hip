@@ -16,16 +16,18 @@
 //                (depth bits, Gaussian id) is exactly what a STABLE sort by (tile, depth bits) gives within a tile,
 //                since the reference emits instances in Gaussian-index order.  Tiles whose list does not fit LDS
 //                (> 4096 entries) are sorted by the same workgroup as LDS-sized runs merged in global memory.
+//                When the plain four-wave blend forward follows (Options::blend_sort), it sorts the lists of up to 512 keys itself
+//                (blend_fwd.hip): only the long-list launch is left here.
 // The result (point_list, ranges, sorted keys) is bit-identical to the global radix back-end; traffic drops from
 // ~150 B to ~30 B per instance and the kernel count from 20 to 4.
 #include <atomic>
 #include <type_traits>
 #include "expand.h"
 #include "gsr_common.h"
+#include "tile_sort.h"
 
 namespace gsr {
 
-constexpr int SORT_WAVE_MAX = 512;   // longest list one wave sorts by itself (8 runs of 64 + rank merge); longer ones: bucket_sort_kernel
 constexpr int SORT_BIG = 2048;  // keys the workgroup sort of lists > 512 handles in LDS (two buffers of 16 KB); longer lists: chunks + global merge
 
 // One returning atomic per instance: the value it returns is the instance's arrival rank inside its tile, kept in
@@ -708,47 +710,6 @@ __device__ __forceinline__ void wave_sort_tile(const uint64_t *b, int n, uint32_
 }
 
 
-// ---- sort by runs + rank merge (lists of 65 .. 512 keys) ---------------------------------------------------------------
-// A full bitonic network over NREG x 64 keys costs log^2 stages over every register and needs a power-of-two size: a tile with
-// 260 keys pays for 512.  Here every register is sorted ACROSS THE LANES as its own run of 64 (21 stages, all runs in lockstep),
-// the runs go to LDS, and each key finds its final position as  lane + sum over the other runs of (keys smaller than it)  by a
-// binary search per run (keys are unique: they contain the Gaussian id).  Work grows with the number of runs actually needed
-// (5 runs for 260 keys), not with the next power of two; at C3 (lists of ~240, up to 355) this is ~2x fewer instructions.
-constexpr int MERGE_MAX_RUNS = 8;
-
-template <int J>
-__device__ __forceinline__ uint64_t lane_xor_u64(uint64_t v) {
-  uint32_t lo, hi;
-  if constexpr (J < 32) {  // ds_swizzle bit-mode: lane ^ J inside each group of 32
-    lo = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)v, (J << 10) | 0x1F);
-    hi = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)(v >> 32), (J << 10) | 0x1F);
-  } else {
-    lo = (uint32_t)__shfl_xor((int)(uint32_t)v, J, WAVE);
-    hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), J, WAVE);
-  }
-  return ((uint64_t)hi << 32) | lo;
-}
-// one compare-exchange stage (block size K, distance J) of an ASCENDING bitonic sort of 64 keys held one per lane
-template <int NRUN, int K, int J>
-__device__ __forceinline__ void run_stage(uint64_t (&key)[NRUN], uint32_t lane) {
-  const bool take_min = ((lane & (uint32_t)J) == 0) == ((lane & (uint32_t)K) == 0 || K == WAVE);
-#pragma unroll
-  for (int r = 0; r < NRUN; r++) {
-    const uint64_t mine = key[r], other = lane_xor_u64<J>(mine);
-    key[r] = take_min ? (mine < other ? mine : other) : (mine > other ? mine : other);
-  }
-}
-template <int NRUN, int K, int J>
-__device__ __forceinline__ void run_merge(uint64_t (&key)[NRUN], uint32_t lane) {
-  run_stage<NRUN, K, J>(key, lane);
-  if constexpr (J > 1) run_merge<NRUN, K, J / 2>(key, lane);
-}
-template <int NRUN, int K>
-__device__ __forceinline__ void run_levels(uint64_t (&key)[NRUN], uint32_t lane) {
-  run_merge<NRUN, K, K / 2>(key, lane);
-  if constexpr (K < WAVE) run_levels<NRUN, K * 2>(key, lane);
-}
-
 template <int NRUN>
 __device__ __forceinline__ void wave_sort_tile_runs(const uint64_t *b, int n, uint32_t tile, uint32_t base, uint32_t *point_list,
                                                     uint64_t *keys_sorted, uint32_t lane, uint64_t *s_runs) {
@@ -771,13 +732,7 @@ __device__ __forceinline__ void wave_sort_tile_runs(const uint64_t *b, int n, ui
 #pragma unroll
     for (int o = 0; o < NRUN; o++) {
       if (o == r) continue;
-      const uint64_t *run = s_runs + o * WAVE;
-      // branch-free: the searches of a key in the other runs (and of the lane's other keys) are independent chains of LDS
-      // reads the scheduler can overlap
-      uint32_t c = 0u;
-#pragma unroll
-      for (int step = WAVE / 2; step >= 1; step >>= 1) c += run[c + step - 1] < k ? (uint32_t)step : 0u;
-      rank += run[WAVE - 1] < k ? (uint32_t)WAVE : c;  // whole run smaller?
+      rank += rank_in_run(s_runs + o * WAVE, k);
     }
     if (k != ~0ull) {  // not padding
       point_list[base + rank] = (uint32_t)k;
@@ -1042,7 +997,7 @@ bool bucket_uses_hist(const Options &opt, int P, size_t tiles, size_t capacity) 
 
 int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int grid_y, size_t capacity, bool device_sized,
                    BinningState &b, uint2 *ranges, uint32_t *order, uint32_t *ckpt_base, int segments, uint32_t *dev_status,
-                   bool check_prefilter, bool scan_fused, const Options &opt, hipStream_t stream, int debug) {
+                   bool check_prefilter, bool scan_fused, bool fwd_sorts, const Options &opt, hipStream_t stream, int debug) {
   const size_t tiles = (size_t)grid_x * grid_y;
   if (grid_x >= 1024 || grid_y >= 1024) {
     set_error("image larger than 16368 px per side is not supported by the packed tile rect");
@@ -1057,8 +1012,8 @@ int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int 
   int n_sb, hbv;
   hist_split(P, n_sb, hbv);
   const bool hist = bucket_uses_hist(opt, P, tiles, capacity);
-  if (scan_fused && !hist) {
-    set_error("bucket_binning: the fused block scan needs the histogram path");
+  if ((scan_fused || fwd_sorts) && !hist) {
+    set_error("bucket_binning: the fused block scan and the sort in the forward need the histogram path");
     return GSR_EINVAL;
   }
   if (hist) {
@@ -1119,6 +1074,12 @@ int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int 
   // binning 61 -> 71..77 us, render() as one graph 0.803 -> 0.836 ms.)
   const unsigned big_grid = 4u * (unsigned)cu_count();  // SORT_BIG keys = 32 KB of LDS each: up to five per CU
   const unsigned n_big = (unsigned)(tiles < big_grid ? tiles : big_grid);
+  if (fwd_sorts) {  // the short lists are sorted by the forward that walks them (blend_fwd.hip); only the work list is left here
+    hipLaunchKernelGGL((bucket_sort_kernel<SORT_BIG, SORT_WAVE_MAX, true>), dim3(n_big), dim3(256), 0, stream, ranges, b.keys_a, b.vals_s,
+                       b.keys_s, b.tile_cursor, g.total + 2);
+    GSR_LAUNCH_CHECK(stream, debug);
+    return GSR_OK;
+  }
   if (hist && opt.bucket_sort_merged) {  // (the work list is complete: the scatter kernel's order builder wrote it)
     hipLaunchKernelGGL((bucket_sort_both_kernel<SORT_BIG, SORT_WAVE_MAX, true>), dim3(n_big + (unsigned)((tiles + 3) / 4)), dim3(256), 0,
                        stream, ranges, b.keys_a, b.vals_s, b.keys_s, b.tile_cursor, g.total + 2, n_big, (uint32_t)tiles);

@@ -4,7 +4,8 @@
 //   * a 16x16 tile is four 8x8 quadrants; a lane owns one pixel of a quadrant (lane = (y&7)*8 + (x&7));
 //   * a wave owns SLOTS quadrants of a tile and never synchronises with another wave; with SLOTS = 1 the four waves of a tile
 //     are launched as one workgroup only to share a CU (one L1 for the tile's records) (SLOTS = 1, 2 or 4 pixels per lane; tuning knob
-//     "blend_fwd_waves" = 4/SLOTS waves per tile).  Waves never synchronise with each other: no __syncthreads;
+//     "blend_fwd_waves" = 4/SLOTS waves per tile).  Waves never synchronise with each other during the walk (the only __syncthreads
+//     are the two of the sort prologue, workgroup_sort_tile);
 //   * the wave walks the tile's depth-sorted instance list 64 entries at a time.  Lane j fetches entry j's 48-byte
 //     SplatRec and tests its conservative cull box (hx, hy: outside it alpha < 1/255 for sure) against the wave's
 //     pixel rectangle; a ballot + mbcnt compacts the survivors into LDS (three float4 planes, original list
@@ -15,6 +16,7 @@
 // stop (without blending) when T*(1-alpha) < 1e-4, alpha image = sum of weights, depth image = sum z*w.  Culling is
 // conservative, so it only removes work whose outcome is "skip".
 #include "gsr_common.h"
+#include "tile_sort.h"
 
 #ifndef FWD_FULL_ROWS
 #define FWD_FULL_ROWS false
@@ -38,10 +40,52 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t n) {
 template <int SLOTS, int CE>
 constexpr int fwd_wpg() { return SLOTS == 1 ? (CE > 0 ? FWD_FEATURE_WPG : 4) : 1; }
 
+// Prologue of blend_forward_kernel<1, 0> when the binning left the short lists unsorted (Options::blend_sort): the four waves sort
+// their tile's n <= SORT_WAVE_MAX keys as the binning's wave sort does (runs of 64 across the lanes, then every key's rank by binary
+// search in the other runs), with the runs spread over the waves (wave w owns runs w and w + 4) in LDS that the walk reuses later.
+// point_list and keys_sorted get what the binning's sort writes; s_ids keeps the sorted ids for the walk.  Workgroup-uniform call.
+__device__ __forceinline__ void workgroup_sort_tile(const uint64_t *b, int n, uint32_t tile, uint32_t base, uint32_t *point_list,
+                                                    uint64_t *keys_sorted, uint32_t wv, uint32_t lane, uint64_t *s_runs,
+                                                    uint32_t *s_ids) {
+  const int nruns = (n + WAVE - 1) / WAVE, r0 = (int)wv, r1 = (int)wv + 4;
+  uint64_t key[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int i = (r0 + 4 * j) * WAVE + (int)lane;
+    key[j] = i < n ? b[i] : ~0ull;  // padding sorts behind every real key and is never stored
+  }
+  if (r1 < nruns) {
+    run_levels<2, 2>(key, lane);
+  } else if (r0 < nruns) {
+    uint64_t k1[1] = {key[0]};
+    run_levels<1, 2>(k1, lane);
+    key[0] = k1[0];
+  }
+  if (r0 < nruns) s_runs[r0 * WAVE + (int)lane] = key[0];
+  if (r1 < nruns) s_runs[r1 * WAVE + (int)lane] = key[1];
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int r = r0 + 4 * j;
+    if (r >= nruns) break;
+    const uint64_t k = key[j];
+    uint32_t rank = lane;  // keys of its own run in front of it
+#pragma unroll
+    for (int o = 0; o < MERGE_MAX_RUNS; o++)
+      if (o != r && o < nruns) rank += rank_in_run(s_runs + o * WAVE, k);
+    if (k != ~0ull) {
+      point_list[base + rank] = (uint32_t)k;
+      keys_sorted[base + rank] = ((uint64_t)tile << 32) | (k >> 32);
+      s_ids[rank] = (uint32_t)k;
+    }
+  }
+  __syncthreads();  // s_ids complete; every read of the runs done before the walk writes its rows over them
+}
+
 template <int SLOTS, int CE>
 __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_kernel(const BlendFwdArgs a) {
   // SLOTS == 1: the four quadrant waves of a tile form ONE workgroup -- still independent of each other, there is no workgroup
-  // barrier anywhere -- so that they run on one CU and fetch the tile's records through one L1: 104 -> 97 us at C3, 153 -> 146 us
+  // barrier outside the sort prologue -- so that they run on one CU and fetch the tile's records through one L1: 104 -> 97 us at C3, 153 -> 146 us
   // in the render() frame (the same layout changed nothing for the backward kernels, which keep one wave per workgroup).
   // With 18 extra channels a workgroup is HALF a tile (two waves, 15 KB of LDS): four-wave workgroups of 30.7 KB were only placed
   // four to a CU although five fit on paper.
@@ -92,6 +136,17 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
   const uint2 range = a.ranges[tile];
   const int n = (int)(range.y - range.x);
   list_priority(a.order, n, a.list_prio);
+  // (a.unsorted is set only for this kernel's <1, 0> instantiation: forward_sorts_lists)
+  constexpr bool SORTS = SLOTS == 1 && CE == 0;
+  __shared__ uint32_t s_ids[SORTS ? SORT_WAVE_MAX : 1];
+  const bool ids_in_lds = SORTS && a.unsorted && n <= SORT_WAVE_MAX;  // (workgroup-uniform)
+  if constexpr (SORTS) {
+    static_assert(sizeof(s0_all) == MERGE_MAX_RUNS * WAVE * sizeof(uint64_t), "the runs alias s0_all");
+    if (ids_in_lds && n > 0)
+      workgroup_sort_tile(a.unsorted + range.x, n, tile, range.x, a.point_list, a.keys_sorted, wv, lane,
+                          reinterpret_cast<uint64_t *>(s0_all), s_ids);
+  }
+  auto list_at = [&](int i) -> uint32_t { return ids_in_lds ? s_ids[i] : a.point_list[range.x + i]; };
 
   float pxf[SLOTS], pyf[SLOTS], T[SLOTS], C0[SLOTS], C1[SLOTS], C2[SLOTS], Dp[SLOTS], Wt[SLOTS];
   float X[SLOTS][CE > 0 ? CE : 1];
@@ -130,13 +185,13 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
   float4 p0 = make_float4(0, 0, 0, 0), p1 = p0, p2 = p0;  // records of the current batch (prefetched)
   uint32_t id_cur = 0;
   if ((int)lane < n) {
-    id_cur = a.point_list[range.x + lane];
+    id_cur = list_at((int)lane);
     const float4 *src = reinterpret_cast<const float4 *>(a.recs + id_cur);
     p0 = src[0];
     p1 = src[1];
     p2 = src[2];
   }
-  if ((int)lane + WAVE < n) id_a = a.point_list[range.x + lane + WAVE];
+  if ((int)lane + WAVE < n) id_a = list_at((int)lane + WAVE);
   // checkpoints for the backward's list segments (gsr_common.h "list segments"): the accumulators as they stand in front of entry
   // k * seg_len, k = 1 .. nseg - 1, and once more at the end (record nseg - 1); a wave that retires early leaves its final state in
   // every record it has not reached
@@ -206,7 +261,7 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
       p1 = src[1];
       p2 = src[2];
     }
-    if (idx + 2 * WAVE < n) id_a = a.point_list[range.x + idx + 2 * WAVE];
+    if (idx + 2 * WAVE < n) id_a = list_at(idx + 2 * WAVE);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -743,9 +798,17 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
 
 #endif  // GSR_BUILD_EXPERIMENTS
 
+bool forward_sorts_lists(const Options &opt, int n_extra) {
+  return opt.blend_sort && n_extra == 0 && opt.blend_layout == 0 && opt.blend_fwd_waves == 4;  // blend_forward_kernel<1, 0> below
+}
+
 int launch_blend_forward(const BlendFwdArgs &a, const Options &opt, hipStream_t stream) {
   const unsigned tiles = (unsigned)(a.grid_x * a.grid_y);
   if (tiles == 0) return GSR_OK;
+  if (a.unsorted && !forward_sorts_lists(opt, a.CE)) {
+    set_error("blend forward: unsorted lists need blend_forward_kernel<1, 0>");
+    return GSR_EINVAL;
+  }
   const unsigned slots = tile_slots_max(a.grid_x, a.grid_y);
   if (a.CE != 0) {
     if (a.CE != CE_MAX || !a.extra || !a.out_extra) {

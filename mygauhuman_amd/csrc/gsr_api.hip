@@ -129,6 +129,9 @@ static int set_option(Options &o, const char *key, int v) {
   } else if (!strcmp(key, "bucket_sort_merged")) {
     if (v != 0 && v != 1) return bad("0 or 1");
     o.bucket_sort_merged = v;
+  } else if (!strcmp(key, "blend_sort")) {
+    if (v != 0 && v != 1) return bad("0 or 1");
+    o.blend_sort = v;
   } else if (!strcmp(key, "tile_order")) {
     if (v < 0 || v > 3) return bad("0 (natural order), 1 (longest lists first), 2 / 3 (2 x 2 / 4 x 2 tile blocks by summed length, a block per XCD)");
     o.tile_order = v;
@@ -450,13 +453,17 @@ int forward_stage_b(const FwdIn &in, const GeomState &geom, BinningState &bin, c
   const int grid_x = (in.width + TILE - 1) / TILE, grid_y = (in.height + TILE - 1) / TILE;
   const size_t tiles = (size_t)grid_x * grid_y;
   int rc;
+  // the short lists are sorted by the forward itself when it can (forward_sorts_lists) and the binning takes its histogram path
+  // (whose scatter kernel builds the work list of the long ones)
+  const bool bucket = R_host < 0 || opt.binning_mode == GSR_BINNING_TILE_BUCKET;
+  const bool fwd_sorts = bucket && forward_sorts_lists(opt, in.n_extra) && bucket_uses_hist(opt, in.P, tiles, capacity);
   prof_begin(PROF_BINNING, stream);
-  if (R_host < 0 || opt.binning_mode == GSR_BINNING_TILE_BUCKET) {
+  if (bucket) {
     // list segments need the forward variant that writes the checkpoints (blend_forward_kernel<1, .>)
     const int segments = (opt.tile_order == 1 && opt.blend_layout == 0 && !opt.blend_fwd_dma && (in.n_extra != 0 || opt.blend_fwd_waves == 4))
                              ? (opt.blend_segments | (opt.blend_tail_cut << 8)) : 0;
     rc = bucket_binning(geom, radii, in.P, grid_x, grid_y, capacity, R_host < 0, bin, img.ranges, img.order, img.ckpt_base, segments,
-                        dev_status, in.prefiltered != 0, scan_fused, opt, stream, in.debug & 1);
+                        dev_status, in.prefiltered != 0, scan_fused, fwd_sorts, opt, stream, in.debug & 1);
     if (rc != GSR_OK) return rc;
   } else {
     const size_t R = (size_t)R_host;
@@ -484,6 +491,8 @@ int forward_stage_b(const FwdIn &in, const GeomState &geom, BinningState &bin, c
   fa.ranges = img.ranges;
   fa.order = img.order;
   fa.point_list = bin.vals_s;
+  fa.unsorted = fwd_sorts ? bin.keys_a : nullptr;
+  fa.keys_sorted = bin.keys_s;
   fa.recs = geom.recs;
   fa.W = in.width;
   fa.H = in.height;

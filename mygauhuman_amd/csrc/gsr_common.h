@@ -238,6 +238,7 @@ struct Options {
   int tile_order = 1;        // blend kernels visit the tiles longest list first, spread over the XCDs (1, default) or in the natural order (0)
   int bucket_hist = 1;       // atomics-free counting of the tile-bucket back-end (LDS histograms per workgroup); 0 = global atomics
   int bucket_sort_merged = 1;  // histogram path: the per-tile sorts of short and long lists as ONE launch (0: two launches)
+  int blend_sort = 1;          // histogram path + blend_forward_kernel<1, 0>: the forward's workgroup sorts its tile's short list itself
   int bucket_cstride = 4;    // counters per 64-byte line = 16 / stride (interleaved A/B at C3, us of binning: 1: 112, 2: 106, 4: 100, 16: 126)
   int blend_fwd_dma = 0;     // 1: fused multi-feature forward with the feature rows staged half a batch ahead by global -> LDS DMA
                              // (parity-green experiment, SLOWER: 191 vs 144 us in the render() frame, profiles/r3_fwd_dma_experiment.txt)
@@ -287,8 +288,12 @@ int launch_tile_ranges(size_t R, const uint64_t *keys_sorted, uint2 *ranges, siz
 struct BlendFwdArgs {
   const uint32_t *order;  // ImageState::order (null: natural order)
   const uint2 *ranges;
-  const uint32_t *point_list;
+  uint32_t *point_list;  // written only when `unsorted` is set
   const SplatRec *recs;
+  // non-null (blend_forward_kernel<1, 0> only): the binning left the lists of up to SORT_WAVE_MAX entries unsorted in this bucket
+  // (depth bits << 32 | Gaussian id); the forward sorts them and writes point_list and keys_sorted as the binning's sort would
+  const uint64_t *unsorted;
+  uint64_t *keys_sorted;
   int W, H, grid_x, grid_y;
   const float *bg;  // device pointer [3]
   float *out_color, *out_depth, *out_alpha, *final_T;
@@ -302,6 +307,8 @@ struct BlendFwdArgs {
   unsigned long long *trace;  // measurement (gsr_debug_wave_trace): per wave {start, end (100 MHz ticks), list length, batches walked}
 };
 int launch_blend_forward(const BlendFwdArgs &a, const Options &opt, hipStream_t stream);
+// does launch_blend_forward take the kernel that can sort its tiles' short lists itself (BlendFwdArgs::unsorted)?
+bool forward_sorts_lists(const Options &opt, int n_extra);
 // is ImageState::order to be used (its mode word)?  Then the work items are NOT remapped to keep neighbouring tiles on one XCD:
 // the long lists at the front of the order must spread over all eight XCDs (hardware assigns workgroup i to XCD i % 8).  With
 // the remap they all landed on XCD 0: 377 instead of 212 us in the render() frame.
@@ -410,7 +417,7 @@ int launch_query_recs(int what, int P, const GeomState &g, void *dst, hipStream_
 // g.total, write dev_status[0] = R, dev_status[1] = (R > capacity) | 2 * (prefilter violation) and render nothing on overflow.
 int bucket_binning(const GeomState &g, const int *radii, int P, int grid_x, int grid_y, size_t capacity, bool device_sized,
                    BinningState &b, uint2 *ranges, uint32_t *order, uint32_t *ckpt_base, int segments, uint32_t *dev_status,
-                   bool check_prefilter, bool scan_fused, const Options &opt, hipStream_t stream, int debug);
+                   bool check_prefilter, bool scan_fused, bool fwd_sorts, const Options &opt, hipStream_t stream, int debug);
 // true if bucket_binning will take its atomics-free histogram path (which can also do the block-sums scan: scan_fused)
 bool bucket_uses_hist(const Options &opt, int P, size_t tiles, size_t capacity);
 // the per-tile sorts of the tile-bucket back-end over caller-built buckets (see binning_bucket.hip)
