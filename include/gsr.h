@@ -805,6 +805,46 @@ size_t gsr_pbr_loss_workspace_floats(void);
 int gsr_pbr_loss_forward(const gsr_pbr_loss *loss, float *workspace, gsr_stream_t stream);
 int gsr_pbr_loss_backward(const gsr_pbr_loss *loss, const float *workspace, gsr_stream_t stream);
 
+/* ---- SSIM on the bound-mask crop without a host read (train.py:269-281, :318-321; csrc/ssim_crop.hip) ----
+ * gsr_bounding_rect: rect[4] = (x, y, w, h) of the nonzero pixels of mask[H][W] with OpenCV's boundingRect meaning -- x, y the
+ * smallest column and row that hold a nonzero pixel, w = largest column - x + 1, h likewise, (0, 0, 0, 0) for an all-zero mask.
+ * mask_dtype: GSR_MASK_F32 (nonzero = != 0.0f) or GSR_MASK_U8 (uint8 / bool bytes).  Two launches (per-workgroup boxes into
+ * `workspace`, gsr_bounding_rect_workspace_ints() ints, then one workgroup folds them); every workspace word that is read has
+ * been written by the same call, so the workspace needs no initialisation and none between calls.  No memset, no host read. */
+enum { GSR_MASK_F32 = 0, GSR_MASK_U8 = 1 };
+size_t gsr_bounding_rect_workspace_ints(void);
+int gsr_bounding_rect(int height, int width, const void *mask, int mask_dtype, int *rect, int *workspace, gsr_stream_t stream);
+
+/* SSIM of the crop img[:, y:y+h, x:x+w] for up to GSR_SSIM_CROP_MAX_GROUPS (img1, img2) pairs that share H, W and the device
+ * rectangle `rect` (int32 (x, y, w, h); clipped to the frame on the device).  The reference's ssim() pads with zeros, so the crop's
+ * SSIM is the full-frame SSIM map of the two images zeroed outside the rectangle, averaged over the rectangle: the kernels launch
+ * over the whole frame and take the rectangle from device memory.
+ *   forward:  value[g][0] = sum over the rectangle of the map / (planes[g] * w * h); dA / dB / dC[g] ([planes][H][W], all three or
+ *             none) get the derivative maps inside the rectangle only (the rest is left as it was and never read).  Per-workgroup
+ *             sums go to `workspace` (gsr_ssim_crop_workspace_floats() floats) and are added in a fixed order: two calls on the
+ *             same inputs give the same bits.
+ *   backward: d_img1[g] ([planes][H][W] contiguous, null = skip the group) = the SSIM backward with the upstream gradient
+ *             upstream[g][0] / (planes[g] * w * h) (upstream[g] null: 1) inside the rectangle and 0 outside, written in full.
+ * img1 is read at the element strides img1_stride[g] (plane, row, pixel); img2 is contiguous and takes no gradient.
+ * An empty rectangle (w == 0 or h == 0) gives value 0 and an all-zero gradient (the reference raises there: conv2d refuses an
+ * empty crop). */
+#define GSR_SSIM_CROP_MAX_GROUPS 4
+typedef struct gsr_ssim_crop {
+  int groups, height, width;
+  const int *rect;                                    /* device int32[4] */
+  int planes[GSR_SSIM_CROP_MAX_GROUPS];               /* 1..65535 in total */
+  const float *img1[GSR_SSIM_CROP_MAX_GROUPS];
+  long long img1_stride[GSR_SSIM_CROP_MAX_GROUPS][3];
+  const float *img2[GSR_SSIM_CROP_MAX_GROUPS];
+  float *dA[GSR_SSIM_CROP_MAX_GROUPS], *dB[GSR_SSIM_CROP_MAX_GROUPS], *dC[GSR_SSIM_CROP_MAX_GROUPS];
+  float *value[GSR_SSIM_CROP_MAX_GROUPS];             /* forward: [1] each */
+  const float *upstream[GSR_SSIM_CROP_MAX_GROUPS];    /* backward: [1] each, or null */
+  float *d_img1[GSR_SSIM_CROP_MAX_GROUPS];            /* backward */
+} gsr_ssim_crop;
+size_t gsr_ssim_crop_workspace_floats(int total_planes, int height, int width);
+int gsr_ssim_crop_forward(const gsr_ssim_crop *crop, float *workspace, gsr_stream_t stream);
+int gsr_ssim_crop_backward(const gsr_ssim_crop *crop, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,19 @@ class PbrLoss(C.Structure):
         [(k, C.c_void_p) for k in ("loss", "terms", "upstream", "d_rgb", "d_a", "d_b", "d_mask")] + [("d_g", C.c_void_p * 2)]
 
 
+SSIM_CROP_MAX_GROUPS = 4
+MASK_F32, MASK_U8 = 0, 1  # mask_dtype of gsr_bounding_rect
+
+
+class SsimCrop(C.Structure):
+    """gsr_ssim_crop (include/gsr.h): SSIM of up to four (img1, img2) groups on the rectangle held in device memory."""
+    _G = SSIM_CROP_MAX_GROUPS
+    _fields_ = [("groups", C.c_int), ("height", C.c_int), ("width", C.c_int), ("rect", C.c_void_p), ("planes", C.c_int * _G),
+                ("img1", C.c_void_p * _G), ("img1_stride", (C.c_longlong * 3) * _G), ("img2", C.c_void_p * _G),
+                ("dA", C.c_void_p * _G), ("dB", C.c_void_p * _G), ("dC", C.c_void_p * _G), ("value", C.c_void_p * _G),
+                ("upstream", C.c_void_p * _G), ("d_img1", C.c_void_p * _G)]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -79,6 +92,8 @@ SYMBOLS = [
     "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
     "gsr_pbr_loss_workspace_floats", "gsr_pbr_loss_forward", "gsr_pbr_loss_backward",
     "gsr_pose_refiner_forward", "gsr_pose_refiner_backward",
+    "gsr_bounding_rect_workspace_ints", "gsr_bounding_rect", "gsr_ssim_crop_workspace_floats", "gsr_ssim_crop_forward",
+    "gsr_ssim_crop_backward",
 ]
 
 GSR_OK = 0
@@ -267,6 +282,14 @@ def _load():
     lib.gsr_pose_refiner_backward.argtypes = [C.c_int, C.c_int, C.c_int, fp, ll, ll, C.POINTER(fp), C.POINTER(fp), fp,
                                               C.POINTER(fp), C.POINTER(fp), fp, vp]
     lib.gsr_pose_refiner_forward.restype = lib.gsr_pose_refiner_backward.restype = C.c_int
+    lib.gsr_bounding_rect_workspace_ints.argtypes = []
+    lib.gsr_bounding_rect_workspace_ints.restype = sz
+    lib.gsr_bounding_rect.argtypes = [C.c_int, C.c_int, vp, C.c_int, ip, ip, vp]
+    lib.gsr_ssim_crop_workspace_floats.argtypes = [C.c_int] * 3
+    lib.gsr_ssim_crop_workspace_floats.restype = sz
+    lib.gsr_ssim_crop_forward.argtypes = [C.POINTER(SsimCrop), fp, vp]
+    lib.gsr_ssim_crop_backward.argtypes = [C.POINTER(SsimCrop), vp]
+    lib.gsr_bounding_rect.restype = lib.gsr_ssim_crop_forward.restype = lib.gsr_ssim_crop_backward.restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

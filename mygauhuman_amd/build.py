@@ -28,6 +28,7 @@ SOURCES = [
     ("sh_exchange.hip", []),
     ("rows.hip", []),
     ("ssim.hip", []),
+    ("ssim_crop.hip", []),
     ("gemv.hip", []),
     ("loss.hip", []),
     ("probe.hip", []),

@@ -10,30 +10,9 @@
 //   backward: ONE kernel -- dL/dimg1(p) = conv(g A)(p) + 2 img1(p) conv(g B)(p) + img2(p) conv(g C)(p), g = dL/dmap, the same
 //             separable window over the three maps (the window is symmetric, zero padding on both sides).
 #include "gsr_common.h"
+#include "ssim_window.h"
 
 namespace gsr {
-
-constexpr int SS_T = 16, SS_R = 5, SS_IN = SS_T + 2 * SS_R;  // tile, window radius, staged extent (26)
-
-struct SsimWindow {
-  float w[11];
-};
-// gaussian(11, 1.5) normalised (utils/loss_utils.py:25-27), evaluated in double on the host like the reference's Python floats
-static SsimWindow make_window() {
-  SsimWindow s;
-  double g[11], sum = 0.0;
-  for (int i = 0; i < 11; i++) {
-    g[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-    sum += g[i];
-  }
-  // the reference builds a float32 tensor of the unnormalised values, then divides by their float32 sum
-  float gf[11], sf = 0.f;
-  for (int i = 0; i < 11; i++) gf[i] = (float)g[i];
-  for (int i = 0; i < 11; i++) sf += gf[i];
-  for (int i = 0; i < 11; i++) s.w[i] = gf[i] / sf;
-  (void)sum;
-  return s;
-}
 
 __global__ __launch_bounds__(SS_T *SS_T) void ssim_forward_kernel(int H, int W, const float *img1, const float *img2, SsimWindow win,
                                                                   float *map, float *dA, float *dB, float *dC) {
