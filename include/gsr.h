@@ -845,6 +845,50 @@ size_t gsr_ssim_crop_workspace_floats(int total_planes, int height, int width);
 int gsr_ssim_crop_forward(const gsr_ssim_crop *crop, float *workspace, gsr_stream_t stream);
 int gsr_ssim_crop_backward(const gsr_ssim_crop *crop, gsr_stream_t stream);
 
+/* ---- fused Adam step with the densification statistics (train.py:401-423; csrc/adam.hip) ----
+ * The update rule of torch.optim.Adam(betas, eps, weight_decay = 0, amsgrad = False, maximize = False) for up to
+ * GSR_ADAM_MAX_ARRAYS tensors of up to GSR_ADAM_MAX_GROUPS parameter groups in two launches: one that advances the step counters,
+ * one that streams every tensor once.  `arrays` and `groups` are HOST arrays (the pointers in them device pointers):
+ *   array:  param, grad, exp_avg, exp_avg_sq of `count` floats (count == 0: nothing is moved, the counter still advances; the
+ *           pointers may then be null), `group` its entry of `groups`, `step_slot` its counter steps[step_slot] (float32, one
+ *           slot per array: a slot may appear once per call);
+ *   group:  beta1, beta2 in [0, 1), eps > 0, clamp_min (-inf = none; applied to the parameter after the update), and the
+ *           learning rate: lr_table[lr_slot] when the device table lr_table is not null (the form a captured graph needs: the caller
+ *           rewrites the table in place between replays), else the by-value lr.
+ * Accesses are 16 bytes wide for an array whose four pointers are all 16-byte aligned and 4 bytes wide otherwise.
+ * stats (may be null; P == 0 = nothing): rows i < P with filter[i] != 0 get
+ *   grad_accum[i] += sqrt(gx^2 + gy^2) with (gx, gy) = grad[i * grad_stride + 0 / 1],  denom[i] += 1,
+ *   max_radii[i] = max(max_radii[i], radii[i]);          (scene/gaussian_model.py:764-766, train.py:403)
+ * the other rows are not written.  Every element is owned by one lane (no atomics): a call gives the same bits every time.
+ * No host read, no allocation, no memset; debug != 0 synchronises the stream and reports what the kernels raised.
+ * gsr_stats_update is the statistics block alone (one launch); gsr_adam_chunk_floats() the floats one workgroup takes at a
+ * time (an array of n floats occupies ceil(n / chunk) consecutive entries of the launch's flattened work list). */
+#define GSR_ADAM_MAX_ARRAYS 64
+#define GSR_ADAM_MAX_GROUPS 16
+typedef struct gsr_adam_array {
+  float *param;
+  const float *grad;
+  float *exp_avg, *exp_avg_sq;
+  long long count;
+  int group, step_slot;
+} gsr_adam_array;
+typedef struct gsr_adam_group {
+  double beta1, beta2;
+  float lr, eps, clamp_min;
+  int lr_slot;
+} gsr_adam_group;
+typedef struct gsr_adam_stats {
+  int P, grad_stride;          /* rows; floats between two rows of grad (>= 2) */
+  const float *grad;           /* screen-space gradient, columns 0 and 1 are read */
+  const unsigned char *filter; /* [P] uint8 / bool bytes */
+  const int *radii;            /* [P] */
+  float *grad_accum, *denom, *max_radii; /* [P] each */
+} gsr_adam_stats;
+int gsr_adam_chunk_floats(void);
+int gsr_adam_step(int n_arrays, const gsr_adam_array *arrays, int n_groups, const gsr_adam_group *groups, const float *lr_table,
+                  float *steps, const gsr_adam_stats *stats, int debug, gsr_stream_t stream);
+int gsr_stats_update(const gsr_adam_stats *stats, int debug, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

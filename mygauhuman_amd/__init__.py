@@ -8,6 +8,7 @@ mirrors the reference's operator surface:
   mygauhuman_amd.gaussian_renderer.render     <- gaussian_renderer/__init__.py
   mygauhuman_amd.pbr, mygauhuman_amd.nvdiffrast <- pbr/ (CubemapLight, pbr_shading) and nvdiffrast.torch.texture
   mygauhuman_amd.baking                       <- baking.py (bake_set: per-Gaussian occlusion)
+  mygauhuman_amd.optim.FusedAdam              <- torch.optim.Adam of scene/gaussian_model.py:283 (+ the statistics of train.py:401-405)
 
 `install_dropin()` registers those modules under the reference's import names so train.py / render.py style
 callers work unmodified.
@@ -30,6 +31,14 @@ import sys
 GRAPH_REPLAY_SAFE = os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") == "0"
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # `mygauhuman_amd.optim` without an import statement of its own.  Loaded on first use: it binds libgsr.so, which does not exist
+    # yet when mygauhuman_amd.build is imported to make it.
+    if name == "optim":
+        return importlib.import_module("mygauhuman_amd.optim")
+    raise AttributeError(f"module 'mygauhuman_amd' has no attribute {name!r}")
 
 
 def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner=False):

@@ -74,6 +74,27 @@ class SsimCrop(C.Structure):
                 ("upstream", C.c_void_p * _G), ("d_img1", C.c_void_p * _G)]
 
 
+ADAM_MAX_ARRAYS, ADAM_MAX_GROUPS = 64, 16
+
+
+class AdamArray(C.Structure):
+    """gsr_adam_array (include/gsr.h): one tensor of the fused Adam step."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("count", C.c_longlong), ("group", C.c_int), ("step_slot", C.c_int)]
+
+
+class AdamGroup(C.Structure):
+    """gsr_adam_group (include/gsr.h): the hyperparameters of one parameter group."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("lr", C.c_float), ("eps", C.c_float), ("clamp_min", C.c_float),
+                ("lr_slot", C.c_int)]
+
+
+class AdamStats(C.Structure):
+    """gsr_adam_stats (include/gsr.h): the densification statistics folded into the step."""
+    _fields_ = [("P", C.c_int), ("grad_stride", C.c_int), ("grad", C.c_void_p), ("filter", C.c_void_p), ("radii", C.c_void_p),
+                ("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii", C.c_void_p)]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -94,6 +115,7 @@ SYMBOLS = [
     "gsr_pose_refiner_forward", "gsr_pose_refiner_backward",
     "gsr_bounding_rect_workspace_ints", "gsr_bounding_rect", "gsr_ssim_crop_workspace_floats", "gsr_ssim_crop_forward",
     "gsr_ssim_crop_backward",
+    "gsr_adam_chunk_floats", "gsr_adam_step", "gsr_stats_update",
 ]
 
 GSR_OK = 0
@@ -290,6 +312,11 @@ def _load():
     lib.gsr_ssim_crop_forward.argtypes = [C.POINTER(SsimCrop), fp, vp]
     lib.gsr_ssim_crop_backward.argtypes = [C.POINTER(SsimCrop), vp]
     lib.gsr_bounding_rect.restype = lib.gsr_ssim_crop_forward.restype = lib.gsr_ssim_crop_backward.restype = C.c_int
+    lib.gsr_adam_chunk_floats.argtypes = []
+    lib.gsr_adam_step.argtypes = [C.c_int, C.POINTER(AdamArray), C.c_int, C.POINTER(AdamGroup), fp, fp, C.POINTER(AdamStats),
+                                  C.c_int, vp]
+    lib.gsr_stats_update.argtypes = [C.POINTER(AdamStats), C.c_int, vp]
+    lib.gsr_adam_chunk_floats.restype = lib.gsr_adam_step.restype = lib.gsr_stats_update.restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",

@@ -37,6 +37,7 @@ SOURCES = [
     ("pbr.hip", []),
     ("bake.hip", ["-ffp-contract=off"]),
     ("pbr_loss.hip", []),
+    ("adam.hip", []),
     ("gsr_api.hip", []),
 ]
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

@@ -133,14 +133,20 @@ def apply_plan(model, plan, reset_stats):
 
 
 # ---------------------------------------------------------------- the reference's operations
-def training_setup(model, lrs, percent_dense=0.01):
-    """lrs: dict group name -> learning rate (position_lr_init * spatial_lr_scale etc., :256-281).  Adam(eps=1e-15)."""
+def training_setup(model, lrs, percent_dense=0.01, fused_step=False):
+    """lrs: dict group name -> learning rate (position_lr_init * spatial_lr_scale etc., :256-281).  Adam(eps=1e-15).
+    fused_step: the optimizer is optim.FusedAdam (two HIP launches per step for all groups, statistics folded in, recordable
+    into a graph) instead of torch.optim.Adam."""
     P, dev = model._xyz.shape[0], model._xyz.device
     model.percent_dense = percent_dense
     model.xyz_gradient_accum = torch.zeros((P, 1), device=dev)
     model.denom = torch.zeros((P, 1), device=dev)
     model.max_radii2D = torch.zeros((P,), device=dev)
     groups = [{"params": [getattr(model, ATTR[g])], "lr": float(lrs.get(g, 0.0)), "name": g} for g in GROUPS]
+    if fused_step:
+        from .optim import FusedAdam
+        model.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        return model.optimizer
     # same update rule as the reference's torch.optim.Adam(l, lr=0.0, eps=1e-15) (:283); on the GPU the fused implementation
     # runs one kernel per group instead of the foreach path's ~8
     model.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15, fused=True if dev.type == "cuda" else None)
