@@ -889,6 +889,49 @@ int gsr_adam_step(int n_arrays, const gsr_adam_array *arrays, int n_groups, cons
                   float *steps, const gsr_adam_stats *stats, int debug, gsr_stream_t stream);
 int gsr_stats_update(const gsr_adam_stats *stats, int debug, gsr_stream_t stream);
 
+/* ---- evaluation "view finish" without a host read (render.py:186-350, train.py:480-540; csrc/eval.hip) ----
+ * Everything the reference's evaluation loop does to one view's images after render() / pbr_shading return, in three launches:
+ *   finish:  one pass over the pixels for all slots.  Per slot and pixel, in the reference's order: GSR_EVAL_FLIP_Z (the ground-truth
+ *            normal of render.py:190-193: n = n * 2 - 1, channel 2 negated, n = (n + 1) / 2, the same operations in the same order);
+ *            GSR_EVAL_FILL: where the bound mask is 0 the value becomes fill = (bg[0] + bg[1] + bg[2] == 0) ? 0 : 1, evaluated on the
+ *            device (render.py:250-253, :264-270); clamp to [0, 1] (NaN stays NaN, as torch.clamp); the float result is written to
+ *            dst, or over src when dst is null; u8 (may be null) gets uint8(min(max(x * 255 + 0.5, 0), 255)), truncating
+ *            (torchvision.utils.save_image), as [H][W][channels] bytes.  For the metric pair the per-channel sums of squared
+ *            differences of the finished values go to per-workgroup partials (double, no atomics).
+ *   ssim:    forward-only SSIM (11 x 11 window, zero padding; utils/loss_utils.py:36-66) of the finished metric pair: no map is written,
+ *            one partial per 16 x 16 tile and plane.
+ *   metrics: one workgroup adds the partials in a fixed order (double) and writes table[counter] = (psnr, ssim) with
+ *            psnr = mean_c 20 log10(1 / sqrt(mse_c)) (utils/image_utils.py:19-21; mse_c == 0 gives +inf) and ssim = sum / (3 H W),
+ *            then stores counter + 1.  counter < 0 or >= capacity: nothing is written to the table and overflow[0] = 1 (sticky).
+ * A slot is read at its element strides (plane, row, pixel), so [C][H][W] images and permuted [H][W][C] ones are taken in place;
+ * dst, when given, has the same strides.  Slots must not overlap one another.  metric_image = metric_gt = -1: no metrics (the
+ * second and third launch are skipped; workspace, counter, table and overflow may then be null).  The workspace
+ * (gsr_eval_workspace_floats() floats, 8-byte aligned) needs no initialisation.  No memset, no host read, no allocation: two calls
+ * on the same inputs write the same bits. */
+#define GSR_EVAL_MAX_SLOTS 16
+enum { GSR_EVAL_FILL = 1, GSR_EVAL_FLIP_Z = 2 };
+typedef struct gsr_eval_slot {
+  float *src;             /* read; finished in place when dst is null */
+  float *dst;             /* or null */
+  unsigned char *u8;      /* [H][W][channels], or null */
+  long long stride[3];    /* elements between planes, rows, pixels of src (and dst) */
+  int channels, flags;    /* 1 or 3; GSR_EVAL_FILL | GSR_EVAL_FLIP_Z (FLIP_Z needs 3 channels) */
+} gsr_eval_slot;
+typedef struct gsr_eval_view {
+  int slots, height, width;
+  gsr_eval_slot slot[GSR_EVAL_MAX_SLOTS];
+  const void *mask;        /* [H][W], device; required when a slot has GSR_EVAL_FILL */
+  int mask_dtype;          /* GSR_MASK_F32 or GSR_MASK_U8 */
+  const float *background; /* device float[3]; required when a slot has GSR_EVAL_FILL */
+  int metric_image, metric_gt; /* slot indices (both 3-channel), or both -1 */
+  int *counter;            /* device int[1]: the row of this view */
+  double *table;           /* device double[capacity][2]: (psnr, ssim) */
+  int capacity;
+  int *overflow;           /* device int[1] */
+} gsr_eval_view;
+size_t gsr_eval_workspace_floats(int height, int width);
+int gsr_eval_view_finish(const gsr_eval_view *view, float *workspace, gsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

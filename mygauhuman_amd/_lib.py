@@ -95,6 +95,24 @@ class AdamStats(C.Structure):
                 ("grad_accum", C.c_void_p), ("denom", C.c_void_p), ("max_radii", C.c_void_p)]
 
 
+EVAL_MAX_SLOTS = 16
+EVAL_FILL, EVAL_FLIP_Z = 1, 2  # slot flags of gsr_eval_view
+
+
+class EvalSlot(C.Structure):
+    """gsr_eval_slot (include/gsr.h): one image of the evaluation view finish."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("u8", C.c_void_p), ("stride", C.c_longlong * 3), ("channels", C.c_int),
+                ("flags", C.c_int)]
+
+
+class EvalView(C.Structure):
+    """gsr_eval_view (include/gsr.h): the images of one view, the bound mask, the device background and the metrics table."""
+    _fields_ = [("slots", C.c_int), ("height", C.c_int), ("width", C.c_int), ("slot", EvalSlot * EVAL_MAX_SLOTS),
+                ("mask", C.c_void_p), ("mask_dtype", C.c_int), ("background", C.c_void_p), ("metric_image", C.c_int),
+                ("metric_gt", C.c_int), ("counter", C.c_void_p), ("table", C.c_void_p), ("capacity", C.c_int),
+                ("overflow", C.c_void_p)]
+
+
 # every symbol include/gsr.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
@@ -116,6 +134,7 @@ SYMBOLS = [
     "gsr_bounding_rect_workspace_ints", "gsr_bounding_rect", "gsr_ssim_crop_workspace_floats", "gsr_ssim_crop_forward",
     "gsr_ssim_crop_backward",
     "gsr_adam_chunk_floats", "gsr_adam_step", "gsr_stats_update",
+    "gsr_eval_workspace_floats", "gsr_eval_view_finish",
 ]
 
 GSR_OK = 0
@@ -317,6 +336,10 @@ def _load():
                                   C.c_int, vp]
     lib.gsr_stats_update.argtypes = [C.POINTER(AdamStats), C.c_int, vp]
     lib.gsr_adam_chunk_floats.restype = lib.gsr_adam_step.restype = lib.gsr_stats_update.restype = C.c_int
+    lib.gsr_eval_workspace_floats.argtypes = [C.c_int, C.c_int]
+    lib.gsr_eval_workspace_floats.restype = sz
+    lib.gsr_eval_view_finish.argtypes = [C.POINTER(EvalView), fp, vp]
+    lib.gsr_eval_view_finish.restype = C.c_int
     lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
     for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
                  "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",
