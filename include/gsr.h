@@ -734,6 +734,28 @@ typedef struct gsr_pbr_shade {
 int gsr_pbr_shade_forward(const gsr_pbr_shade *s, gsr_stream_t stream);
 int gsr_pbr_shade_backward(const gsr_pbr_shade *s, gsr_stream_t stream);
 
+/* The environment light's own share of a PBR step.  base is a 3-channel cube [6][base_n][base_n][3], looked up
+ * exactly as gsr_pbr_texture_forward looks it up (one level, no bias); a zero direction samples 0.  No call reads the device.
+ * gsr_pbr_env_grey (train.py:195-198): out[n] = 0.2989 r + 0.587 g + 0.114 b of clamp(lookup(dirs[n][3]), 0, 1); one launch.
+ * gsr_pbr_env_tv_* (train.py:352-363): loss[0] = mean((e[1:] - e[:-1])^2) + mean((e[:, 1:] - e[:, :-1])^2), e[h][w][3] the lookup
+ *   at dirs[h][w][3], h, w >= 2.  The forward (two launches: per-workgroup partial sums, then one workgroup adds them in a fixed
+ *   order) writes e and its partial sums into workspace (gsr_pbr_env_tv_workspace_floats(h, w) floats, e first); the backward (one
+ *   launch) reads them and ADDS upstream[0] * d loss / d base into d_base: zero it first.  reduce selects how the backward
+ *   splits the samples over workgroups that each sum into an LDS window of d_base and add its non-zero entries to memory once. */
+#define GSR_PBR_ENV_TV_AUTO 0   /* the faster of the two where both apply, else WINDOW */
+#define GSR_PBR_ENV_TV_WINDOW 1 /* the split of gsr_pbr_texture_backward: any base size, few large workgroup shares */
+#define GSR_PBR_ENV_TV_WHOLE 2  /* d_base whole in LDS (it must fit); workgroups of 1,024 samples, at most 256 of them (beyond that a thread takes several samples) */
+int gsr_pbr_env_grey(int base_n, const float *base, int n, const float *dirs, float *out, gsr_stream_t stream);
+size_t gsr_pbr_env_tv_workspace_floats(int h, int w);
+int gsr_pbr_env_tv_forward(int base_n, const float *base, int h, int w, const float *dirs, float *workspace, float *loss,
+                           gsr_stream_t stream);
+int gsr_pbr_env_tv_backward(int base_n, int h, int w, const float *dirs, const float *workspace, const float *upstream,
+                            float *d_base, int reduce, gsr_stream_t stream);
+/* render.py:215-222: out[n][3] = -(R rays[n] / max(|rays[n]|, 1e-12)), R the upper-left 3 x 3 block of
+ * inverse(world_view_transform^T) ([4][4] row-major on the device, inverted in the kernel by cofactors: a singular matrix gives
+ * non-finite directions where torch.inverse raises).  One launch. */
+int gsr_pbr_view_dirs(int n, const float *rays, const float *world_view_transform, float *out, gsr_stream_t stream);
+
 /* ---- Occlusion bake (baking.py bake_set; csrc/bake.hip; DESIGN.md "Occlusion bake") ----
  * gsr_bake_grid is pc_to_grid(points, 10): cell[P] = the compact cell id of each point, the occupied cells numbered in (ix, iy, iz)
  * lexicographic order (torch.unique's), centres[n][3] and cell_idx[n][3] (may be null) for the first *n_cells of 1000 rows, size[3]

@@ -127,6 +127,7 @@ SYMBOLS = [
     "gsr_pbr_texture_forward", "gsr_pbr_texture_backward", "gsr_pbr_cube_mip_forward", "gsr_pbr_cube_mip_backward",
     "gsr_pbr_diffuse_forward", "gsr_pbr_diffuse_backward", "gsr_pbr_specular_forward", "gsr_pbr_specular_backward",
     "gsr_pbr_shade_forward", "gsr_pbr_shade_backward",
+    "gsr_pbr_env_grey", "gsr_pbr_env_tv_workspace_floats", "gsr_pbr_env_tv_forward", "gsr_pbr_env_tv_backward", "gsr_pbr_view_dirs",
     "gsr_bake_grid_workspace_bytes", "gsr_bake_grid", "gsr_bake_plan_bytes", "gsr_bake_plan", "gsr_bake_visibility_workspace_bytes",
     "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
     "gsr_pbr_loss_workspace_floats", "gsr_pbr_loss_forward", "gsr_pbr_loss_backward",
@@ -148,6 +149,7 @@ DEFAULT_TILE_CULL = 1  # tuning knob "tile_cull": exact ellipse-vs-tile culling 
 DEFAULT_BWD_REDUCE = 3
 DEFAULT_TILE_ORDER = 1  # tuning knob "tile_order" (csrc/gsr_common.h: Options)
 DEFAULT_BLEND_LAYOUT = 0  # tuning knob "blend_layout"
+ENV_TV_AUTO, ENV_TV_WINDOW, ENV_TV_WHOLE = 0, 1, 2  # gsr_pbr_env_tv_backward's reduce (include/gsr.h)
 DEFAULT_BLEND_SEGMENTS = 8  # tuning knob "blend_segments": lists >= 8 / 4 x the frame's mean are walked in segments
 
 
@@ -297,6 +299,14 @@ def _load():
     lib.gsr_pbr_shade_forward.argtypes = lib.gsr_pbr_shade_backward.argtypes = [C.POINTER(PbrShade), vp]
     for name in ("texture_forward", "texture_backward", "cube_mip_forward", "cube_mip_backward", "diffuse_forward",
                  "diffuse_backward", "specular_forward", "specular_backward", "shade_forward", "shade_backward"):
+        getattr(lib, "gsr_pbr_" + name).restype = C.c_int
+    lib.gsr_pbr_env_grey.argtypes = [C.c_int, fp, C.c_int, fp, fp, vp]
+    lib.gsr_pbr_env_tv_workspace_floats.argtypes = [C.c_int, C.c_int]
+    lib.gsr_pbr_env_tv_workspace_floats.restype = sz
+    lib.gsr_pbr_env_tv_forward.argtypes = [C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, vp]
+    lib.gsr_pbr_env_tv_backward.argtypes = [C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_int, vp]
+    lib.gsr_pbr_view_dirs.argtypes = [C.c_int, fp, fp, fp, vp]
+    for name in ("env_grey", "env_tv_forward", "env_tv_backward", "view_dirs"):
         getattr(lib, "gsr_pbr_" + name).restype = C.c_int
     sz, u64p = C.c_size_t, C.POINTER(C.c_ulonglong)
     bs = C.POINTER(BakeScene)

@@ -806,3 +806,270 @@ int gsr_pbr_shade_backward(const gsr_pbr_shade *s, gsr_stream_t stream_) {
 }
 
 }  // extern "C"
+
+// ==== The environment light's own share of a PBR step ==========================================================
+// The grey environment map (train.py:195-198), the environment-map TV regulariser (train.py:352-363) and the view directions
+// (render.py:215-222).  A separate section of this file, not a translation unit of its own, because the lookups must be the ones
+// of texture_forward_kernel: cube_footprint and the LDS-window reduction above are used as they are.  No kernel above is changed.
+namespace gsr {
+
+constexpr int ENV_BLOCK = 256;
+// torchvision.transforms.functional.rgb_to_grayscale: l = 0.2989 r + 0.587 g + 0.114 b
+constexpr float GREY_R = 0.2989f, GREY_G = 0.587f, GREY_B = 0.114f;
+
+// the linear cube lookup of texture_forward_kernel (one level, three channels) at direction d[0..2]
+__device__ __forceinline__ void env_sample(const float *__restrict__ base, int N, const float *__restrict__ d, float *e) {
+  e[0] = e[1] = e[2] = 0.f;
+  Taps tp;
+  if (!cube_footprint(d[0], d[1], d[2], N, tp)) return;
+  for (int k = 0; k < 4; k++)
+    if (tp.t[k] >= 0)
+      for (int ch = 0; ch < 3; ch++) e[ch] += tp.w[k] * base[(size_t)tp.t[k] * 3 + ch];
+}
+
+__global__ __launch_bounds__(ENV_BLOCK) void env_grey_kernel(int N, const float *__restrict__ base, int n,
+                                                             const float *__restrict__ dirs, float *__restrict__ out) {
+  const int p = blockIdx.x * ENV_BLOCK + threadIdx.x;
+  if (p >= n) return;
+  float e[3];
+  env_sample(base, N, dirs + (size_t)p * 3, e);
+  const float r = fminf(fmaxf(e[0], 0.f), 1.f), g = fminf(fmaxf(e[1], 0.f), 1.f), b = fminf(fmaxf(e[2], 0.f), 1.f);
+  out[p] = GREY_R * r + GREY_G * g + GREY_B * b;
+}
+
+// sum over a workgroup of ENV_BLOCK threads, in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ float env_block_sum(float v, float *red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if (threadIdx.x % WAVE == 0) red[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  float s = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < ENV_BLOCK / WAVE; i++) s += red[i];
+  return s;
+}
+
+// TV forward, first launch: e[p] = lookup at dirs[p] (kept for the backward) and, per workgroup, the sums of the squared
+// differences to the sample below and to the sample to the right.  A thread looks its two neighbours up itself (the same
+// instructions on the same inputs: the same bits as the neighbour's own e), so no workgroup waits for another.
+__global__ __launch_bounds__(ENV_BLOCK) void env_tv_partial_kernel(int N, const float *__restrict__ base, int h, int w,
+                                                                   const float *__restrict__ dirs, float *__restrict__ e,
+                                                                   float *__restrict__ partials) {
+  __shared__ float red[ENV_BLOCK / WAVE];
+  const int n = h * w, p = blockIdx.x * ENV_BLOCK + threadIdx.x;
+  float sv = 0.f, sh = 0.f;
+  if (p < n) {
+    float e0[3], e1[3];
+    env_sample(base, N, dirs + (size_t)p * 3, e0);
+    for (int c = 0; c < 3; c++) e[(size_t)p * 3 + c] = e0[c];
+    const int x = p % w, y = p / w;
+    if (y + 1 < h) {
+      env_sample(base, N, dirs + (size_t)(p + w) * 3, e1);
+      for (int c = 0; c < 3; c++) sv += (e1[c] - e0[c]) * (e1[c] - e0[c]);
+    }
+    if (x + 1 < w) {
+      env_sample(base, N, dirs + (size_t)(p + 1) * 3, e1);
+      for (int c = 0; c < 3; c++) sh += (e1[c] - e0[c]) * (e1[c] - e0[c]);
+    }
+  }
+  sv = env_block_sum(sv, red);
+  sh = env_block_sum(sh, red);
+  if (threadIdx.x == 0) {
+    partials[2 * blockIdx.x] = sv;
+    partials[2 * blockIdx.x + 1] = sh;
+  }
+}
+
+// TV forward, second launch: one workgroup adds the partials in a fixed order, in double, and forms the two means
+__global__ __launch_bounds__(ENV_BLOCK) void env_tv_finish_kernel(int h, int w, int nblk, const float *__restrict__ partials,
+                                                                  float *__restrict__ loss) {
+  __shared__ double red[2][ENV_BLOCK];
+  double sv = 0.0, sh = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += ENV_BLOCK) {
+    sv += (double)partials[2 * i];
+    sh += (double)partials[2 * i + 1];
+  }
+  red[0][threadIdx.x] = sv;
+  red[1][threadIdx.x] = sh;
+  __syncthreads();
+  for (int s = ENV_BLOCK / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + s];
+      red[1][threadIdx.x] += red[1][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0)
+    loss[0] = (float)(red[0][0] / (3.0 * (double)(h - 1) * (double)w) + red[1][0] / (3.0 * (double)h * (double)(w - 1)));
+}
+
+// TV backward: d e of a sample from its four neighbours in e, through the sample's taps into the LDS window, one flush per
+// workgroup (the reduction of texture_backward_kernel)
+__global__ __launch_bounds__(PBR_BLOCK) void env_tv_backward_kernel(int N, int h, int w, const float *__restrict__ dirs,
+                                                                    const float *__restrict__ e,
+                                                                    const float *__restrict__ upstream, GradSpace gs, int per_wg) {
+  extern __shared__ float lds[];
+  const int lo = blockIdx.y * gs.win;
+  win_zero(lds, gs.win);
+  const int n = h * w;
+  const float up = upstream[0];
+  const float cv = up * (2.f / (3.f * (float)(h - 1) * (float)w)), chz = up * (2.f / (3.f * (float)h * (float)(w - 1)));
+  const int p_begin = blockIdx.x * per_wg, p_end = min(n, p_begin + per_wg);
+  for (int p = p_begin + threadIdx.x; p < p_end; p += blockDim.x) {
+    const int x = p % w, y = p / w;
+    float de[3];
+    for (int c = 0; c < 3; c++) {
+      const size_t o = (size_t)p * 3 + c;
+      const float e0 = e[o];
+      float v = 0.f, z = 0.f;
+      if (y > 0) v += e0 - e[o - (size_t)w * 3];
+      if (y + 1 < h) v -= e[o + (size_t)w * 3] - e0;
+      if (x > 0) z += e0 - e[o - 3];
+      if (x + 1 < w) z -= e[o + 3] - e0;
+      de[c] = cv * v + chz * z;
+    }
+    Taps tp;
+    if (!cube_footprint(dirs[(size_t)p * 3], dirs[(size_t)p * 3 + 1], dirs[(size_t)p * 3 + 2], N, tp)) continue;
+    for (int k = 0; k < 4; k++)
+      if (tp.t[k] >= 0)
+        for (int c = 0; c < 3; c++) win_add(lds, lo, gs.win, tp.t[k] * 3 + c, tp.w[k] * de[c]);
+  }
+  win_flush(lds, lo, gs);
+}
+
+// cofactor (r, c) of the row-major 4 x 4 matrix a
+__device__ __forceinline__ float cofactor4(const float *a, int r, int c) {
+  int ri[3], ci[3];
+  for (int i = 0, k = 0, l = 0; i < 4; i++) {
+    if (i != r) ri[k++] = i;
+    if (i != c) ci[l++] = i;
+  }
+  const float m00 = a[ri[0] * 4 + ci[0]], m01 = a[ri[0] * 4 + ci[1]], m02 = a[ri[0] * 4 + ci[2]];
+  const float m10 = a[ri[1] * 4 + ci[0]], m11 = a[ri[1] * 4 + ci[1]], m12 = a[ri[1] * 4 + ci[2]];
+  const float m20 = a[ri[2] * 4 + ci[0]], m21 = a[ri[2] * 4 + ci[1]], m22 = a[ri[2] * 4 + ci[2]];
+  const float d = m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+  return ((r + c) & 1) ? -d : d;
+}
+
+constexpr int VD_PER_THREAD = 4;
+
+// out[p] = -(R ray[p] / max(|ray[p]|, 1e-12)), R = the upper-left 3 x 3 block of inverse(wvt^T): the full 4 x 4 cofactor inverse,
+// formed once per workgroup (ten cofactors on ten threads; a singular matrix gives non-finite directions)
+__global__ __launch_bounds__(ENV_BLOCK) void view_dirs_kernel(int n, const float *__restrict__ rays,
+                                                              const float *__restrict__ wvt, float *__restrict__ out) {
+  __shared__ float a[16], cof[10], R[9];
+  const int t = threadIdx.x;
+  if (t < 16) a[t] = wvt[(t % 4) * 4 + t / 4];  // a = wvt^T
+  __syncthreads();
+  if (t < 10) cof[t] = t < 9 ? cofactor4(a, t / 3, t % 3) : cofactor4(a, 0, 3);
+  __syncthreads();
+  if (t < 9) {
+    const float det = a[0] * cof[0] + a[1] * cof[1] + a[2] * cof[2] + a[3] * cof[9];
+    R[t] = cof[(t % 3) * 3 + t / 3] / det;  // inverse[i][j] = cofactor[j][i] / det
+  }
+  __syncthreads();
+  float r[9];
+  for (int i = 0; i < 9; i++) r[i] = R[i];
+  const size_t first = (size_t)blockIdx.x * (ENV_BLOCK * VD_PER_THREAD) + t;
+  for (int k = 0; k < VD_PER_THREAD; k++) {
+    const size_t p = first + (size_t)k * ENV_BLOCK;
+    if (p >= (size_t)n) break;
+    const float x = rays[p * 3], y = rays[p * 3 + 1], z = rays[p * 3 + 2];
+    const float len = fmaxf(sqrtf(x * x + y * y + z * z), 1e-12f);
+    const float nx = x / len, ny = y / len, nz = z / len;
+    for (int i = 0; i < 3; i++) out[p * 3 + i] = -(nx * r[i * 3] + ny * r[i * 3 + 1] + nz * r[i * 3 + 2]);
+  }
+}
+
+static bool env_base_ok(int N, size_t n) { return N >= 1 && N <= 4096 && n <= (size_t)1 << 30; }
+static int env_tv_blocks(int h, int w) { return (h * w + ENV_BLOCK - 1) / ENV_BLOCK; }
+
+}  // namespace gsr
+
+extern "C" {
+
+int gsr_pbr_env_grey(int base_n, const float *base, int n, const float *dirs, float *out, gsr_stream_t stream_) {
+  using namespace gsr;
+  if (!env_base_ok(base_n, n < 0 ? 0 : (size_t)n) || n < 0 || !base || (n > 0 && (!dirs || !out))) {
+    set_error("gsr_pbr_env_grey: bad arguments (base [6][n][n][3], 1 <= n <= 4096; dirs [n][3]; out [n])");
+    return GSR_EINVAL;
+  }
+  if (n == 0) return GSR_OK;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(env_grey_kernel, dim3((n + ENV_BLOCK - 1) / ENV_BLOCK), dim3(ENV_BLOCK), 0, stream, base_n, base, n, dirs,
+                     out);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+size_t gsr_pbr_env_tv_workspace_floats(int h, int w) {
+  if (h < 1 || w < 1 || (size_t)h * (size_t)w > (size_t)1 << 28) return 0;
+  return (size_t)h * w * 3 + 2 * (size_t)gsr::env_tv_blocks(h, w);
+}
+
+int gsr_pbr_env_tv_forward(int base_n, const float *base, int h, int w, const float *dirs, float *workspace, float *loss,
+                           gsr_stream_t stream_) {
+  using namespace gsr;
+  if (h < 2 || w < 2 || (size_t)h * (size_t)w > (size_t)1 << 28 || !env_base_ok(base_n, 0) || !base || !dirs || !workspace ||
+      !loss) {
+    set_error("gsr_pbr_env_tv_forward: bad arguments (base [6][n][n][3], 1 <= n <= 4096; dirs [h][w][3], h, w >= 2)");
+    return GSR_EINVAL;
+  }
+  const int nblk = env_tv_blocks(h, w);
+  float *partials = workspace + (size_t)h * w * 3;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(env_tv_partial_kernel, dim3(nblk), dim3(ENV_BLOCK), 0, stream, base_n, base, h, w, dirs, workspace, partials);
+  GSR_LAUNCH_CHECK(stream, 0);
+  hipLaunchKernelGGL(env_tv_finish_kernel, dim3(1), dim3(ENV_BLOCK), 0, stream, h, w, nblk, partials, loss);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+int gsr_pbr_env_tv_backward(int base_n, int h, int w, const float *dirs, const float *workspace, const float *upstream,
+                            float *d_base, int reduce, gsr_stream_t stream_) {
+  using namespace gsr;
+  if (h < 2 || w < 2 || (size_t)h * (size_t)w > (size_t)1 << 28 || !env_base_ok(base_n, 0) || !dirs || !workspace || !upstream ||
+      !d_base || reduce < 0 || reduce > 2) {
+    set_error("gsr_pbr_env_tv_backward: bad arguments (dirs [h][w][3], h, w >= 2; reduce 0..2)");
+    return GSR_EINVAL;
+  }
+  const int n = h * w;
+  GradSpace gs{};
+  gs.off[0] = 0;
+  gs.ptr[0] = d_base;
+  gs.off[1] = gs.total = 6 * base_n * base_n * 3;
+  int nwg, groups, per_wg;
+  bwd_grid(n, gs, nwg, groups, per_wg);  // GSR_PBR_ENV_TV_WINDOW: the split of texture_backward_kernel
+  if (groups > 1 && reduce == GSR_PBR_ENV_TV_WHOLE) {
+    set_error("gsr_pbr_env_tv_backward: the gradient of a base of %d does not fit in LDS (reduce = whole)", base_n);
+    return GSR_EINVAL;
+  }
+  if (groups == 1 && reduce != GSR_PBR_ENV_TV_WINDOW) {  // the whole gradient in LDS: one pass of PBR_BLOCK samples per workgroup
+    nwg = max(1, min(256, (n + PBR_BLOCK - 1) / PBR_BLOCK));
+    per_wg = (n + nwg - 1) / nwg;
+  }
+  const size_t lds = (size_t)gs.win * sizeof(float);
+  GSR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(env_tv_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(env_tv_backward_kernel, dim3(nwg, groups), dim3(PBR_BLOCK), lds, stream, base_n, h, w, dirs, workspace,
+                     upstream, gs, per_wg);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+int gsr_pbr_view_dirs(int n, const float *rays, const float *world_view_transform, float *out, gsr_stream_t stream_) {
+  using namespace gsr;
+  if (n < 0 || (size_t)n > (size_t)1 << 30 || !world_view_transform || (n > 0 && (!rays || !out))) {
+    set_error("gsr_pbr_view_dirs: bad arguments (rays [n][3], world_view_transform [4][4], out [n][3])");
+    return GSR_EINVAL;
+  }
+  if (n == 0) return GSR_OK;
+  const int per = ENV_BLOCK * VD_PER_THREAD;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(view_dirs_kernel, dim3((n + per - 1) / per), dim3(ENV_BLOCK), 0, stream, n, rays, world_view_transform, out);
+  GSR_LAUNCH_CHECK(stream, 0);
+  return GSR_OK;
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@ class CubemapLight(nn.Module):
         base = torch.rand(6, base_res, base_res, 3, dtype=torch.float32, device=device) * scale + bias
         self.base = nn.Parameter(base)
         self.register_parameter("env_base", self.base)
+        self._grey_dirs = {}  # (h, w, device) -> grey_envmap's direction grid
 
     def _check(self):
         if self.base.dim() != 4 or self.base.shape[-1] != 3:
@@ -71,6 +72,33 @@ class CubemapLight(nn.Module):
             roughness = (idx / (len(self.specular) - 2)) * (self.MAX_ROUGHNESS - self.MIN_ROUGHNESS) + self.MIN_ROUGHNESS
             self.specular[idx] = specular_cubemap(self.specular[idx], roughness, cutoff)
         self.specular[-1] = specular_cubemap(self.specular[-1], 1.0, cutoff)
+
+    def grey_envmap(self, res: List[int] = [16, 32], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """train.py:195-198 / render.py:164-167 in one launch: Grayscale()(export_envmap(return_img=True, res).permute(2, 0, 1)
+        .clamp(0, 1)), [1, h, w], without a gradient.  The direction grid (export_envmap's own expressions) is built once per
+        (res, device) at the first call: call once before recording a graph, so that the grid is not allocated in the graph's pool
+        (graph.GraphedFrame's warm-up does).  Grids of other devices are dropped, so a light moved with .to() keeps one.  out= is
+        written in place and returned, so a captured graph refreshes the map render(envmap=...) reads."""
+        from . import env
+        if self.base.dim() != 4 or self.base.shape[0] != 6 or self.base.shape[1] != self.base.shape[2] or self.base.shape[3] != 3:
+            raise NotImplementedError(f"CubemapLight: 3-channel cube lights [6, N, N, 3] only, base has shape {tuple(self.base.shape)}")
+        if len(res) != 2 or int(res[0]) < 1 or int(res[1]) < 1:
+            raise ValueError(f"grey_envmap: res must be two positive sizes, got {list(res)}")
+        dev = self.base.device
+        if not self.base.is_cuda:
+            raise RuntimeError("grey_envmap: the light must live on a HIP device (no CPU path)")
+        key = (int(res[0]), int(res[1]), dev)
+        cache = self.__dict__.setdefault("_grey_dirs", {})
+        if key not in cache:
+            for old in [k for k in cache if k[2] != dev]:
+                del cache[old]
+            gy, gx = torch.meshgrid(torch.linspace(0.0, 1.0, key[0], device=dev), torch.linspace(-1.0, 1.0, key[1], device=dev),
+                                    indexing="ij")
+            sintheta, costheta = torch.sin(gy * np.pi), torch.cos(gy * np.pi)
+            sinphi, cosphi = torch.sin(gx * np.pi), torch.cos(gx * np.pi)
+            cache[key] = torch.stack((sintheta * sinphi, costheta, -sintheta * cosphi), dim=-1).contiguous()
+        with torch.no_grad():
+            return env.grey_envmap(self.base, cache[key], out)
 
     def export_envmap(self, filename: Optional[str] = None, res: List[int] = [256, 512],
                       return_img: bool = False) -> Optional[torch.Tensor]:
