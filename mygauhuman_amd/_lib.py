@@ -1,6 +1,7 @@
 """ctypes binding of libgsr.so (the C ABI declared in include/gsr.h).
 
 There is NO fallback: if the HIP library is missing or does not load, importing this module raises."""
+import contextlib
 import ctypes as C
 import os
 
@@ -113,30 +114,159 @@ class EvalView(C.Structure):
                 ("overflow", C.c_void_p)]
 
 
-# every symbol include/gsr.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "gsr_version", "gsr_has_experiments", "gsr_target_arch", "gsr_last_error", "gsr_set_binning_mode", "gsr_get_binning_mode", "gsr_set_tuning", "gsr_set_stream_tuning", "gsr_clear_stream_tuning", "gsr_profile_enable", "gsr_profile_reset", "gsr_profile_read", "gsr_debug_wave_trace", "gsr_debug_clock_probe",
-    "gsr_mark_visible", "gsr_rasterize_forward", "gsr_rasterize_backward", "gsr_query_state",
-    "gsr_geometry_bytes", "gsr_image_bytes", "gsr_binning_bytes", "gsr_rasterize_forward_async",
-    "gsr_alpha_mask_loss_backward", "gsr_phase1_loss_partials", "gsr_phase1_loss_forward", "gsr_rasterize_backward_phase1_loss", "gsr_rasterize_backward_alpha_mask_loss", "gsr_rasterize_forward_ex", "gsr_rasterize_forward_async_ex", "gsr_rasterize_backward_ex",
-    "gsr_dist2_workspace_bytes", "gsr_dist2", "gsr_sort_workspace_bytes", "gsr_sort_pairs_u64",
-    "gsr_sort_pairs_u32", "gsr_lbs_forward", "gsr_lbs_backward", "gsr_lbs_backward_workgroups", "gsr_lbs_workspace_bytes", "gsr_lbs_grid_build", "gsr_lbs_forward_grid", "gsr_lbs_forward_cached", "gsr_lbs_nn_cache_bytes", "gsr_smpl_pose_forward", "gsr_smpl_pose_backward", "gsr_sh_view_pack", "gsr_sh_grad_from_views", "gsr_sh_view_pack_posed", "gsr_sh_grad_from_views_posed", "gsr_step_status", "gsr_step_finish", "gsr_knn_self", "gsr_knn_nearest", "gsr_gather_rows", "gsr_ssim_forward", "gsr_ssim_backward", "gsr_gemv_rows", "gsr_gemv_rows_t", "gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_lbs_offset_mlp_packed_floats", "gsr_lbs_offset_mlp_pack", "gsr_lbs_offset_mlp_forward", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward", "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_set_precision",
-    "gsr_lbs_forward_nj", "gsr_lbs_forward_grid_nj", "gsr_lbs_forward_cached_nj", "gsr_lbs_backward_nj", "gsr_body_pose_forward",
-    "gsr_body_pose_backward", "gsr_lbs_offset_mlp_packed_floats_nb", "gsr_lbs_offset_mlp_pack_nb", "gsr_lbs_offset_mlp_forward_nb",
-    "gsr_debug_lbs_offset_mlp_forward_bf16x3_nb", "gsr_lbs_offset_mlp_backward_workspace_floats_nb", "gsr_lbs_offset_mlp_backward_nb",
-    "gsr_pbr_texture_forward", "gsr_pbr_texture_backward", "gsr_pbr_cube_mip_forward", "gsr_pbr_cube_mip_backward",
-    "gsr_pbr_diffuse_forward", "gsr_pbr_diffuse_backward", "gsr_pbr_specular_forward", "gsr_pbr_specular_backward",
-    "gsr_pbr_shade_forward", "gsr_pbr_shade_backward",
-    "gsr_pbr_env_grey", "gsr_pbr_env_tv_workspace_floats", "gsr_pbr_env_tv_forward", "gsr_pbr_env_tv_backward", "gsr_pbr_view_dirs",
-    "gsr_bake_grid_workspace_bytes", "gsr_bake_grid", "gsr_bake_plan_bytes", "gsr_bake_plan", "gsr_bake_visibility_workspace_bytes",
-    "gsr_bake_visibility", "gsr_bake_expand", "gsr_bake_env_reduce",
-    "gsr_pbr_loss_workspace_floats", "gsr_pbr_loss_forward", "gsr_pbr_loss_backward",
-    "gsr_pose_refiner_forward", "gsr_pose_refiner_backward",
-    "gsr_bounding_rect_workspace_ints", "gsr_bounding_rect", "gsr_ssim_crop_workspace_floats", "gsr_ssim_crop_forward",
-    "gsr_ssim_crop_backward",
-    "gsr_adam_chunk_floats", "gsr_adam_step", "gsr_stats_update",
-    "gsr_eval_workspace_floats", "gsr_eval_view_finish",
-]
+# The prototypes of include/gsr.h, the ONE place a new entry point is bound:  name: (return type, parameters, STREAM | PLAIN).
+# STREAM = the function's last parameter is the gsr_stream_t, which is NOT written in the list (_load() appends it, call() passes
+# it).  tests/test_abi_table_host.py holds every line against the header.  Device pointers travel as integers (_P).
+_I, _U, _F, _Z, _LL, _P = C.c_int, C.c_uint, C.c_float, C.c_size_t, C.c_longlong, C.c_void_p
+_S, _IP, _PP, _U64P = C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong)
+STREAM, PLAIN = True, False
+_RASTER_IN = [_I, _I, _I, _P, _I, _I] + [_P] * 5 + [_F] + [_P] * 5 + [_F, _F, _I] + [_P] * 4 + [_I]  # P .. debug of the forwards
+_RASTER_BWD = [_I, _I, _I, _I, _P, _I, _I] + [_P] * 5 + [_F] + [_P] * 5 + [_F, _F] + [_P] * 4  # P .. image_buffer of the backwards
+_LBS_IN = [_I, _I] + [_P] * 19  # P, V, query .. world_normals
+_ATTR_IN = [_I, _I, _I] + [_P] * 4 + [_F] + [_P] * 5  # P, sh_degree, M, means3D .. occlusion
+
+TABLE = {
+    "gsr_version": (_I, [], PLAIN),
+    "gsr_has_experiments": (_I, [], PLAIN),
+    "gsr_target_arch": (_S, [], PLAIN),
+    "gsr_last_error": (_S, [], PLAIN),
+    "gsr_set_binning_mode": (_I, [_I], PLAIN),
+    "gsr_get_binning_mode": (_I, [], PLAIN),
+    "gsr_set_tuning": (_I, [_S, _I], PLAIN),
+    "gsr_set_stream_tuning": (_I, [_P, _S, _I], PLAIN),
+    "gsr_clear_stream_tuning": (_I, [], STREAM),
+    "gsr_profile_enable": (_I, [_U], PLAIN),
+    "gsr_profile_reset": (_I, [], PLAIN),
+    "gsr_profile_read": (_I, [_I, C.POINTER(C.c_double), C.POINTER(C.c_long)], PLAIN),
+    "gsr_debug_wave_trace": (_I, [_P, _Z], PLAIN),
+    "gsr_debug_clock_probe": (_I, [_I, _I, _P], STREAM),
+    # rasterizer
+    "gsr_mark_visible": (_I, [_I, _P, _P, _P, _P], STREAM),
+    "gsr_rasterize_forward": (_I, [ALLOC_FN, _P] * 3 + _RASTER_IN + [_IP], STREAM),
+    "gsr_geometry_bytes": (_Z, [_I], PLAIN),
+    "gsr_image_bytes": (_Z, [_I, _I], PLAIN),
+    "gsr_binning_bytes": (_Z, [_Z, _I, _I], PLAIN),
+    "gsr_rasterize_forward_async": (_I, [_P, _P, _Z, _P] + _RASTER_IN + [_P], STREAM),
+    "gsr_rasterize_backward": (_I, _RASTER_BWD + [_P] * 12 + [_I], STREAM),
+    "gsr_phase1_loss_partials": (_Z, [], PLAIN),
+    "gsr_phase1_loss_forward": (_I, [_I, _I, C.POINTER(Phase1LossStruct), _P], STREAM),
+    "gsr_alpha_mask_loss_backward": (_I, [_I, _I, _P, _P, _P, _P, _F, _P, _P], STREAM),
+    "gsr_rasterize_backward_alpha_mask_loss": (_I, _RASTER_BWD + [_P, _P, _P, _F] + [_P] * 9 + [_I, _I], STREAM),
+    "gsr_query_state": (_I, [_I] * 5 + [_P] * 4, STREAM),
+    # simple-knn, sorts, k-NN, row gather
+    "gsr_dist2_workspace_bytes": (_Z, [_I], PLAIN),
+    "gsr_dist2": (_I, [_I, _P, _P, _P, _Z], STREAM),
+    "gsr_sort_workspace_bytes": (_Z, [_Z], PLAIN),
+    "gsr_sort_pairs_u64": (_I, [_Z, _P, _P, _P, _P, _I, _P, _Z], STREAM),
+    "gsr_sort_pairs_u32": (_I, [_Z, _P, _P, _P, _P, _I, _P, _Z], STREAM),
+    "gsr_knn_self": (_I, [_I, _P, _I, _P, _P, _P, _Z], STREAM),
+    "gsr_knn_nearest": (_I, [_I, _P, _I, _P, _P, _P, _P, _Z], STREAM),
+    "gsr_gather_rows": (_I, [_I, _PP, _PP, _IP, _IP, _I, _P], STREAM),
+    # skinning, pose chain, pose blend shapes
+    "gsr_lbs_workspace_bytes": (_Z, [_I], PLAIN),
+    "gsr_lbs_grid_build": (_I, [_I, _P, _P, _Z], STREAM),
+    "gsr_lbs_nn_cache_bytes": (_Z, [_I], PLAIN),
+    "gsr_lbs_forward": (_I, _LBS_IN, STREAM),
+    "gsr_lbs_forward_grid": (_I, _LBS_IN + [_P, _Z, _I], STREAM),
+    "gsr_lbs_forward_cached": (_I, _LBS_IN + [_P, _Z, _P, _Z, _I], STREAM),
+    "gsr_lbs_backward_workgroups": (_I, [_I], PLAIN),
+    "gsr_lbs_backward": (_I, [_I, _I] + [_P] * 20, STREAM),
+    "gsr_smpl_pose_forward": (_I, [_P, _P, _P, _IP, _P, _P], STREAM),
+    "gsr_smpl_pose_backward": (_I, [_P, _P, _P, _IP] + [_P] * 5, STREAM),
+    "gsr_gemv_rows": (_I, [_I, _I, _P, _P, _P], STREAM),
+    "gsr_gemv_rows_t": (_I, [_I, _I, _P, _P, _P], STREAM),
+    # view-parallel exchange
+    "gsr_sh_view_pack": (_I, [_I, _P, _P, _P], STREAM),
+    "gsr_sh_grad_from_views": (_I, [_I] * 4 + [_P, _P, _Z, _F, _P, _P], STREAM),
+    "gsr_sh_view_pack_posed": (_I, [_I, _P, _P, _P, _P, _P, _Z, _Z], STREAM),
+    "gsr_sh_grad_from_views_posed": (_I, [_I, _I, _I, _P, _Z, _Z, _Z, _F, _P, _P, _P], STREAM),
+    "gsr_step_status": (_I, [_I, _P, _P, _F, _P, _P], STREAM),
+    "gsr_step_finish": (_I, [_P, _P, _Z, _Z, _F, _P, _P], STREAM),
+    # losses
+    "gsr_ssim_forward": (_I, [_I] * 3 + [_P] * 6, STREAM),
+    "gsr_ssim_backward": (_I, [_I] * 3 + [_P] * 3 + [_F] + [_P] * 4, STREAM),
+    "gsr_bounding_rect_workspace_ints": (_Z, [], PLAIN),
+    "gsr_bounding_rect": (_I, [_I, _I, _P, _I, _P, _P], STREAM),
+    "gsr_ssim_crop_workspace_floats": (_Z, [_I] * 3, PLAIN),
+    "gsr_ssim_crop_forward": (_I, [C.POINTER(SsimCrop), _P], STREAM),
+    "gsr_ssim_crop_backward": (_I, [C.POINTER(SsimCrop)], STREAM),
+    "gsr_pbr_loss_workspace_floats": (_Z, [], PLAIN),
+    "gsr_pbr_loss_forward": (_I, [C.POINTER(PbrLoss), _P], STREAM),
+    "gsr_pbr_loss_backward": (_I, [C.POINTER(PbrLoss), _P], STREAM),
+    # per-frame activations and attributes
+    "gsr_model_activations_forward": (_I, [_I] + [_P] * 11, STREAM),
+    "gsr_model_activations_backward": (_I, [_I] + [_P] * 16, STREAM),
+    "gsr_model_activations_backward_acc": (_I, [_I] + [_P] * 17, STREAM),
+    "gsr_frame_attributes_forward": (_I, _ATTR_IN + [_P] * 3 + [_P] * 3, STREAM),
+    "gsr_frame_attributes_backward": (_I, _ATTR_IN + [_P] * 3 + [_P] * 3 + [_P] * 10, STREAM),
+    "gsr_frame_attributes_forward_split": (_I, _ATTR_IN + [_P] * 4 + [_P] * 3, STREAM),
+    "gsr_frame_attributes_backward_split": (_I, _ATTR_IN + [_P] * 4 + [_P] * 3 + [_P] * 11, STREAM),
+    "gsr_frame_attributes_backward_acc": (_I, _ATTR_IN + [_P] * 4 + [_P] * 3 + [_P] * 11 + [_P], STREAM),
+    # networks
+    "gsr_lbs_offset_mlp_packed_floats": (_Z, [], PLAIN),
+    "gsr_lbs_offset_mlp_pack": (_I, [_PP, _PP, _P], STREAM),
+    "gsr_lbs_offset_mlp_forward": (_I, [_I, _P, _P, _P], STREAM),
+    "gsr_lbs_offset_mlp_set_precision": (_I, [_I], PLAIN),
+    "gsr_debug_lbs_offset_mlp_forward_bf16x3": (_I, [_I, _P, _P, _P], STREAM),
+    "gsr_lbs_offset_mlp_backward_workspace_floats": (_Z, [_I], PLAIN),
+    "gsr_lbs_offset_mlp_backward": (_I, [_I, _P, _P, _P, _P, _PP, _PP], STREAM),
+    "gsr_pose_refiner_forward": (_I, [_I, _I, _I, _P, _LL, _LL, _PP, _PP, _P], STREAM),
+    "gsr_pose_refiner_backward": (_I, [_I, _I, _I, _P, _LL, _LL, _PP, _PP, _P, _PP, _PP, _P], STREAM),
+    # image-based lighting
+    "gsr_pbr_texture_forward": (_I, [C.POINTER(PbrTexture), _I, _P, _P, _P], STREAM),
+    "gsr_pbr_texture_backward": (_I, [C.POINTER(PbrTexture), _I, _P, _P, _P, _P, _P], STREAM),
+    "gsr_pbr_cube_mip_forward": (_I, [_I, _I, _P, _P], STREAM),
+    "gsr_pbr_cube_mip_backward": (_I, [_I, _I, _P, _P], STREAM),
+    "gsr_pbr_diffuse_forward": (_I, [_I, _P, _P], STREAM),
+    "gsr_pbr_diffuse_backward": (_I, [_I, _P, _P], STREAM),
+    "gsr_pbr_specular_forward": (_I, [_I, _F, _F, _P, _P, _P], STREAM),
+    "gsr_pbr_specular_backward": (_I, [_I, _F, _F, _P, _P, _P], STREAM),
+    "gsr_pbr_shade_forward": (_I, [C.POINTER(PbrShade)], STREAM),
+    "gsr_pbr_shade_backward": (_I, [C.POINTER(PbrShade)], STREAM),
+    "gsr_pbr_env_grey": (_I, [_I, _P, _I, _P, _P], STREAM),
+    "gsr_pbr_env_tv_workspace_floats": (_Z, [_I, _I], PLAIN),
+    "gsr_pbr_env_tv_forward": (_I, [_I, _P, _I, _I, _P, _P, _P], STREAM),
+    "gsr_pbr_env_tv_backward": (_I, [_I, _I, _I, _P, _P, _P, _P, _I], STREAM),
+    "gsr_pbr_view_dirs": (_I, [_I, _P, _P, _P], STREAM),
+    # occlusion bake
+    "gsr_bake_grid_workspace_bytes": (_Z, [], PLAIN),
+    "gsr_bake_grid": (_I, [_I, _P, _P, _P, _P, _P, _IP, _P, _Z], STREAM),
+    "gsr_bake_plan_bytes": (_Z, [_I, _I], PLAIN),
+    "gsr_bake_plan": (_I, [C.POINTER(BakeScene), _P, _Z, _U64P], STREAM),
+    "gsr_bake_visibility_workspace_bytes": (_Z, [_I, _Z], PLAIN),
+    "gsr_bake_visibility": (_I, [C.POINTER(BakeScene), _P, _P, _P, _Z, _U64P], STREAM),
+    "gsr_bake_expand": (_I, [_I, _I, _P, _P, _P, _P, _P], STREAM),
+    "gsr_bake_env_reduce": (_I, [_I, _P, _P, _P], STREAM),
+    # optimizer, evaluation
+    "gsr_adam_chunk_floats": (_I, [], PLAIN),
+    "gsr_adam_step": (_I, [_I, C.POINTER(AdamArray), _I, C.POINTER(AdamGroup), _P, _P, C.POINTER(AdamStats), _I], STREAM),
+    "gsr_stats_update": (_I, [C.POINTER(AdamStats), _I], STREAM),
+    "gsr_eval_workspace_floats": (_Z, [_I, _I], PLAIN),
+    "gsr_eval_view_finish": (_I, [C.POINTER(EvalView), _P], STREAM),
+}
+
+
+def _variant(base, lead=(), tail=()):
+    """The prototype of `base` with parameters put in front of its own and behind them (before the stream)."""
+    restype, argtypes, streamed = TABLE[base]
+    return restype, [*lead, *argtypes, *tail], streamed
+
+
+_EX_TAIL = [_P, _I, _P, _I]  # extra_features, n_extra, out_extra, sh_dtype
+TABLE["gsr_rasterize_forward_ex"] = _variant("gsr_rasterize_forward", tail=_EX_TAIL)
+TABLE["gsr_rasterize_forward_async_ex"] = _variant("gsr_rasterize_forward_async", tail=_EX_TAIL)
+TABLE["gsr_rasterize_backward_ex"] = _variant("gsr_rasterize_backward", tail=[_P, _I, _PP, _P, _I])
+TABLE["gsr_rasterize_backward_phase1_loss"] = _variant("gsr_rasterize_backward_ex", tail=[C.POINTER(Phase1LossStruct)])
+# joint-count (_nj, gsr_body_pose_*) and bone-count (_nb) variants: the same arguments after a leading count
+for _n in ("gsr_lbs_forward", "gsr_lbs_forward_grid", "gsr_lbs_forward_cached", "gsr_lbs_backward"):
+    TABLE[_n + "_nj"] = _variant(_n, lead=[_I])
+for _n in ("forward", "backward"):
+    TABLE["gsr_body_pose_" + _n] = _variant("gsr_smpl_pose_" + _n, lead=[_I])
+for _n in ("gsr_lbs_offset_mlp_packed_floats", "gsr_lbs_offset_mlp_pack", "gsr_lbs_offset_mlp_forward",
+           "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward"):
+    TABLE[_n + "_nb"] = _variant(_n, lead=[_I])
+
+SYMBOLS = list(TABLE)  # every symbol include/gsr.h declares (tests check that the library exports all of them)
 
 GSR_OK = 0
 Q = dict(DEPTHS=0, MEANS2D=1, CONIC_OPACITY=2, RGB=3, COV3D=4, TILES_TOUCHED=5, POINT_OFFSETS=6, CLAMPED=7,
@@ -163,198 +293,9 @@ def _load():
             f"{LIB_PATH} not found: build the HIP library first (python -m mygauhuman_amd.build, or "
             "__graft_entry__.build()).  There is no CPU/PyTorch fallback for the rasterizer.")
     lib = C.CDLL(LIB_PATH)
-    vp, fp, ip, sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t  # device pointers travel as integers
-    lib.gsr_version.restype = C.c_int
-    lib.gsr_has_experiments.restype = C.c_int
-    lib.gsr_target_arch.restype = C.c_char_p
-    lib.gsr_last_error.restype = C.c_char_p
-    lib.gsr_set_binning_mode.argtypes = [C.c_int]
-    lib.gsr_get_binning_mode.restype = C.c_int
-    lib.gsr_set_tuning.argtypes = [C.c_char_p, C.c_int]
-    lib.gsr_set_stream_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.gsr_clear_stream_tuning.argtypes = [C.c_void_p]
-    lib.gsr_set_stream_tuning.restype = lib.gsr_clear_stream_tuning.restype = C.c_int
-    lib.gsr_profile_enable.argtypes = [C.c_uint]
-    lib.gsr_debug_wave_trace.argtypes = [C.c_void_p, C.c_size_t]
-    lib.gsr_debug_clock_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.gsr_debug_clock_probe.restype = C.c_int
-    lib.gsr_profile_read.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long)]
-    lib.gsr_mark_visible.argtypes = [C.c_int, fp, fp, fp, vp, vp]
-    lib.gsr_rasterize_forward.argtypes = [
-        ALLOC_FN, vp, ALLOC_FN, vp, ALLOC_FN, vp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp,
-        C.c_float, fp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_int, fp, fp, fp, ip, C.c_int, C.POINTER(C.c_int), vp]
-    lib.gsr_rasterize_backward.argtypes = [
-        C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.c_float, fp, fp, fp, fp, fp,
-        C.c_float, C.c_float, ip, vp, vp, vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, vp]
-    lib.gsr_geometry_bytes.argtypes = [C.c_int]
-    lib.gsr_geometry_bytes.restype = sz
-    lib.gsr_image_bytes.argtypes = [C.c_int, C.c_int]
-    lib.gsr_image_bytes.restype = sz
-    lib.gsr_binning_bytes.argtypes = [sz, C.c_int, C.c_int]
-    lib.gsr_binning_bytes.restype = sz
-    lib.gsr_rasterize_forward_async.argtypes = [
-        vp, vp, sz, vp, C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.c_float, fp, fp, fp, fp, fp,
-        C.c_float, C.c_float, C.c_int, fp, fp, fp, ip, C.c_int, vp, vp]
-    lib.gsr_rasterize_forward_async.restype = C.c_int
-    lib.gsr_alpha_mask_loss_backward.argtypes = [C.c_int, C.c_int, fp, fp, fp, fp, C.c_float, fp, fp, vp]
-    lib.gsr_alpha_mask_loss_backward.restype = C.c_int
-    lib.gsr_rasterize_forward_ex.argtypes = lib.gsr_rasterize_forward.argtypes[:-1] + [fp, C.c_int, fp, C.c_int, vp]
-    lib.gsr_rasterize_forward_async_ex.argtypes = lib.gsr_rasterize_forward_async.argtypes[:-1] + [fp, C.c_int, fp, C.c_int, vp]
-    lib.gsr_rasterize_backward_ex.argtypes = lib.gsr_rasterize_backward.argtypes[:-1] + [fp, C.c_int, C.POINTER(C.c_void_p), fp, C.c_int, vp]
-    lib.gsr_rasterize_backward_alpha_mask_loss.argtypes = (lib.gsr_rasterize_backward.argtypes[:24] + [fp, fp, fp, C.c_float] + [fp] * 9
-                                                           + [C.c_int, C.c_int, vp])
-    lib.gsr_phase1_loss_partials.restype = sz
-    lib.gsr_phase1_loss_forward.argtypes = [C.c_int, C.c_int, C.POINTER(Phase1LossStruct), fp, vp]
-    lib.gsr_phase1_loss_forward.restype = C.c_int
-    lib.gsr_rasterize_backward_phase1_loss.argtypes = lib.gsr_rasterize_backward_ex.argtypes[:-1] + [C.POINTER(Phase1LossStruct), vp]
-    for _n in ("gsr_rasterize_forward_ex", "gsr_rasterize_forward_async_ex", "gsr_rasterize_backward_ex",
-               "gsr_rasterize_backward_alpha_mask_loss", "gsr_rasterize_backward_phase1_loss"):
-        getattr(lib, _n).restype = C.c_int
-    lib.gsr_query_state.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.gsr_dist2_workspace_bytes.argtypes = [C.c_int]
-    lib.gsr_dist2_workspace_bytes.restype = sz
-    lib.gsr_dist2.argtypes = [C.c_int, fp, fp, vp, sz, vp]
-    lib.gsr_sort_workspace_bytes.argtypes = [sz]
-    lib.gsr_sort_workspace_bytes.restype = sz
-    lib.gsr_sort_pairs_u64.argtypes = [sz, vp, vp, vp, vp, C.c_int, vp, sz, vp]
-    lib.gsr_sort_pairs_u32.argtypes = [sz, vp, vp, vp, vp, C.c_int, vp, sz, vp]
-    lib.gsr_lbs_forward.argtypes = [C.c_int, C.c_int] + [fp] * 12 + [ip] + [fp] * 6 + [vp]
-    lib.gsr_lbs_forward_grid.argtypes = [C.c_int, C.c_int] + [fp] * 12 + [ip] + [fp] * 6 + [vp, sz, C.c_int, vp]
-    lib.gsr_lbs_forward_cached.argtypes = [C.c_int, C.c_int] + [fp] * 12 + [ip] + [fp] * 6 + [vp, sz, vp, sz, C.c_int, vp]
-    lib.gsr_lbs_forward_cached.restype = C.c_int
-    lib.gsr_lbs_nn_cache_bytes.argtypes = [C.c_int]
-    lib.gsr_lbs_nn_cache_bytes.restype = sz
-    lib.gsr_lbs_grid_build.argtypes = [C.c_int, fp, vp, sz, vp]
-    lib.gsr_lbs_grid_build.restype = C.c_int
-    lib.gsr_lbs_forward_grid.restype = C.c_int
-    lib.gsr_lbs_workspace_bytes.argtypes = [C.c_int]
-    lib.gsr_lbs_workspace_bytes.restype = sz
-    lib.gsr_smpl_pose_forward.argtypes = [fp, fp, fp, C.POINTER(C.c_int), fp, fp, vp]
-    lib.gsr_smpl_pose_backward.argtypes = [fp, fp, fp, C.POINTER(C.c_int)] + [fp] * 5 + [vp]
-    lib.gsr_smpl_pose_forward.restype = lib.gsr_smpl_pose_backward.restype = C.c_int
-    lib.gsr_sh_view_pack.argtypes = [C.c_int, vp, fp, fp, vp]
-    lib.gsr_sh_grad_from_views.argtypes = [C.c_int] * 4 + [fp, fp, sz, C.c_float, fp, fp, vp]
-    lib.gsr_sh_view_pack.restype = lib.gsr_sh_grad_from_views.restype = C.c_int
-    lib.gsr_step_status.argtypes = [C.c_int, vp, fp, C.c_float, fp, vp, vp]
-    lib.gsr_step_status.restype = C.c_int
-    lib.gsr_sh_view_pack_posed.argtypes = [C.c_int, fp, fp, fp, fp, fp, sz, sz, vp]
-    lib.gsr_sh_grad_from_views_posed.argtypes = [C.c_int, C.c_int, C.c_int, fp, sz, sz, sz, C.c_float, fp, fp, fp, vp]
-    lib.gsr_step_finish.argtypes = [vp, fp, sz, sz, C.c_float, fp, vp, vp]
-    lib.gsr_sh_view_pack_posed.restype = lib.gsr_sh_grad_from_views_posed.restype = lib.gsr_step_finish.restype = C.c_int
-    lib.gsr_knn_self.argtypes = [C.c_int, fp, C.c_int, ip, fp, vp, sz, vp]
-    lib.gsr_knn_nearest.argtypes = [C.c_int, fp, C.c_int, fp, ip, fp, vp, sz, vp]
-    lib.gsr_knn_self.restype = lib.gsr_knn_nearest.restype = C.c_int
-    lib.gsr_gather_rows.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                    C.c_int, ip, vp]
-    lib.gsr_gather_rows.restype = C.c_int
-    lib.gsr_ssim_forward.argtypes = [C.c_int] * 3 + [fp] * 6 + [vp]
-    lib.gsr_ssim_backward.argtypes = [C.c_int] * 3 + [fp] * 3 + [C.c_float] + [fp] * 4 + [vp]
-    lib.gsr_ssim_forward.restype = lib.gsr_ssim_backward.restype = C.c_int
-    lib.gsr_gemv_rows.argtypes = [C.c_int, C.c_int, fp, fp, fp, vp]
-    lib.gsr_gemv_rows_t.argtypes = [C.c_int, C.c_int, fp, fp, fp, vp]
-    lib.gsr_gemv_rows.restype = lib.gsr_gemv_rows_t.restype = C.c_int
-    lib.gsr_lbs_backward.argtypes = [C.c_int, C.c_int, fp, fp, ip] + [fp] * 8 + [fp] * 3 + [fp] * 6 + [vp]
-    # joint-count variants: the same arguments after a leading J
-    for name in ("gsr_lbs_forward", "gsr_lbs_forward_grid", "gsr_lbs_forward_cached", "gsr_lbs_backward"):
-        getattr(lib, name + "_nj").argtypes = [C.c_int] + getattr(lib, name).argtypes
-        getattr(lib, name + "_nj").restype = C.c_int
-    lib.gsr_body_pose_forward.argtypes = [C.c_int] + lib.gsr_smpl_pose_forward.argtypes
-    lib.gsr_body_pose_backward.argtypes = [C.c_int] + lib.gsr_smpl_pose_backward.argtypes
-    lib.gsr_body_pose_forward.restype = lib.gsr_body_pose_backward.restype = C.c_int
-    lib.gsr_lbs_backward_workgroups.argtypes = [C.c_int]
-    lib.gsr_lbs_backward_workgroups.restype = C.c_int
-    lib.gsr_frame_attributes_forward.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 8 + [fp] * 3 + [vp]
-    lib.gsr_frame_attributes_backward.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 8 + [fp] * 3 + [fp] * 10 + [vp]
-    lib.gsr_frame_attributes_forward_split.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [vp]
-    lib.gsr_frame_attributes_backward_split.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [vp]
-    lib.gsr_model_activations_forward.argtypes = [C.c_int] + [fp] * 11 + [vp]
-    lib.gsr_model_activations_backward.argtypes = [C.c_int] + [fp] * 16 + [vp]
-    lib.gsr_model_activations_backward_acc.argtypes = [C.c_int] + [fp] * 17 + [vp]
-    lib.gsr_lbs_offset_mlp_packed_floats.argtypes = []
-    lib.gsr_lbs_offset_mlp_packed_floats.restype = C.c_size_t
-    lib.gsr_lbs_offset_mlp_pack.argtypes = [C.POINTER(fp), C.POINTER(fp), fp, vp]
-    lib.gsr_lbs_offset_mlp_pack.restype = C.c_int
-    lib.gsr_lbs_offset_mlp_forward.argtypes = [C.c_int, fp, fp, fp, vp]
-    lib.gsr_lbs_offset_mlp_forward.restype = C.c_int
-    lib.gsr_debug_lbs_offset_mlp_forward_bf16x3.argtypes = [C.c_int, fp, fp, fp, vp]
-    lib.gsr_debug_lbs_offset_mlp_forward_bf16x3.restype = C.c_int
-    lib.gsr_lbs_offset_mlp_set_precision.argtypes = [C.c_int]
-    lib.gsr_lbs_offset_mlp_set_precision.restype = C.c_int
-    lib.gsr_lbs_offset_mlp_backward_workspace_floats.argtypes = [C.c_int]
-    lib.gsr_lbs_offset_mlp_backward_workspace_floats.restype = C.c_size_t
-    lib.gsr_lbs_offset_mlp_backward.argtypes = [C.c_int, fp, fp, fp, fp, C.POINTER(fp), C.POINTER(fp), vp]
-    lib.gsr_lbs_offset_mlp_backward.restype = C.c_int
-    # bone-count variants: the same arguments after a leading nb (24 or 55)
-    for name in ("gsr_lbs_offset_mlp_packed_floats", "gsr_lbs_offset_mlp_pack", "gsr_lbs_offset_mlp_forward",
-                 "gsr_debug_lbs_offset_mlp_forward_bf16x3", "gsr_lbs_offset_mlp_backward_workspace_floats", "gsr_lbs_offset_mlp_backward"):
-        getattr(lib, name + "_nb").argtypes = [C.c_int] + getattr(lib, name).argtypes
-        getattr(lib, name + "_nb").restype = getattr(lib, name).restype
-    pt = C.POINTER(PbrTexture)
-    lib.gsr_pbr_texture_forward.argtypes = [pt, C.c_int, fp, fp, fp, vp]
-    lib.gsr_pbr_texture_backward.argtypes = [pt, C.c_int, fp, fp, fp, fp, fp, vp]
-    lib.gsr_pbr_cube_mip_forward.argtypes = lib.gsr_pbr_cube_mip_backward.argtypes = [C.c_int, C.c_int, fp, fp, vp]
-    lib.gsr_pbr_diffuse_forward.argtypes = lib.gsr_pbr_diffuse_backward.argtypes = [C.c_int, fp, fp, vp]
-    lib.gsr_pbr_specular_forward.argtypes = [C.c_int, C.c_float, C.c_float, fp, fp, fp, vp]
-    lib.gsr_pbr_specular_backward.argtypes = [C.c_int, C.c_float, C.c_float, fp, fp, fp, vp]
-    lib.gsr_pbr_shade_forward.argtypes = lib.gsr_pbr_shade_backward.argtypes = [C.POINTER(PbrShade), vp]
-    for name in ("texture_forward", "texture_backward", "cube_mip_forward", "cube_mip_backward", "diffuse_forward",
-                 "diffuse_backward", "specular_forward", "specular_backward", "shade_forward", "shade_backward"):
-        getattr(lib, "gsr_pbr_" + name).restype = C.c_int
-    lib.gsr_pbr_env_grey.argtypes = [C.c_int, fp, C.c_int, fp, fp, vp]
-    lib.gsr_pbr_env_tv_workspace_floats.argtypes = [C.c_int, C.c_int]
-    lib.gsr_pbr_env_tv_workspace_floats.restype = sz
-    lib.gsr_pbr_env_tv_forward.argtypes = [C.c_int, fp, C.c_int, C.c_int, fp, fp, fp, vp]
-    lib.gsr_pbr_env_tv_backward.argtypes = [C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_int, vp]
-    lib.gsr_pbr_view_dirs.argtypes = [C.c_int, fp, fp, fp, vp]
-    for name in ("env_grey", "env_tv_forward", "env_tv_backward", "view_dirs"):
-        getattr(lib, "gsr_pbr_" + name).restype = C.c_int
-    sz, u64p = C.c_size_t, C.POINTER(C.c_ulonglong)
-    bs = C.POINTER(BakeScene)
-    lib.gsr_bake_grid_workspace_bytes.argtypes = []
-    lib.gsr_bake_grid_workspace_bytes.restype = sz
-    lib.gsr_bake_grid.argtypes = [C.c_int, fp, fp, fp, fp, fp, C.POINTER(C.c_int), vp, sz, vp]
-    lib.gsr_bake_plan_bytes.argtypes = [C.c_int, C.c_int]
-    lib.gsr_bake_plan_bytes.restype = sz
-    lib.gsr_bake_plan.argtypes = [bs, vp, sz, u64p, vp]
-    lib.gsr_bake_visibility_workspace_bytes.argtypes = [C.c_int, sz]
-    lib.gsr_bake_visibility_workspace_bytes.restype = sz
-    lib.gsr_bake_visibility.argtypes = [bs, vp, fp, vp, sz, u64p, vp]
-    lib.gsr_bake_expand.argtypes = [C.c_int, C.c_int, fp, fp, fp, fp, fp, vp]
-    lib.gsr_bake_env_reduce.argtypes = [C.c_int, fp, fp, fp, vp]
-    for name in ("grid", "plan", "visibility", "expand", "env_reduce"):
-        getattr(lib, "gsr_bake_" + name).restype = C.c_int
-    lib.gsr_pbr_loss_workspace_floats.argtypes = []
-    lib.gsr_pbr_loss_workspace_floats.restype = sz
-    lib.gsr_pbr_loss_forward.argtypes = [C.POINTER(PbrLoss), fp, vp]
-    lib.gsr_pbr_loss_backward.argtypes = [C.POINTER(PbrLoss), fp, vp]
-    lib.gsr_pbr_loss_forward.restype = lib.gsr_pbr_loss_backward.restype = C.c_int
-    ll = C.c_longlong
-    lib.gsr_pose_refiner_forward.argtypes = [C.c_int, C.c_int, C.c_int, fp, ll, ll, C.POINTER(fp), C.POINTER(fp), fp, vp]
-    lib.gsr_pose_refiner_backward.argtypes = [C.c_int, C.c_int, C.c_int, fp, ll, ll, C.POINTER(fp), C.POINTER(fp), fp,
-                                              C.POINTER(fp), C.POINTER(fp), fp, vp]
-    lib.gsr_pose_refiner_forward.restype = lib.gsr_pose_refiner_backward.restype = C.c_int
-    lib.gsr_bounding_rect_workspace_ints.argtypes = []
-    lib.gsr_bounding_rect_workspace_ints.restype = sz
-    lib.gsr_bounding_rect.argtypes = [C.c_int, C.c_int, vp, C.c_int, ip, ip, vp]
-    lib.gsr_ssim_crop_workspace_floats.argtypes = [C.c_int] * 3
-    lib.gsr_ssim_crop_workspace_floats.restype = sz
-    lib.gsr_ssim_crop_forward.argtypes = [C.POINTER(SsimCrop), fp, vp]
-    lib.gsr_ssim_crop_backward.argtypes = [C.POINTER(SsimCrop), vp]
-    lib.gsr_bounding_rect.restype = lib.gsr_ssim_crop_forward.restype = lib.gsr_ssim_crop_backward.restype = C.c_int
-    lib.gsr_adam_chunk_floats.argtypes = []
-    lib.gsr_adam_step.argtypes = [C.c_int, C.POINTER(AdamArray), C.c_int, C.POINTER(AdamGroup), fp, fp, C.POINTER(AdamStats),
-                                  C.c_int, vp]
-    lib.gsr_stats_update.argtypes = [C.POINTER(AdamStats), C.c_int, vp]
-    lib.gsr_adam_chunk_floats.restype = lib.gsr_adam_step.restype = lib.gsr_stats_update.restype = C.c_int
-    lib.gsr_eval_workspace_floats.argtypes = [C.c_int, C.c_int]
-    lib.gsr_eval_workspace_floats.restype = sz
-    lib.gsr_eval_view_finish.argtypes = [C.POINTER(EvalView), fp, vp]
-    lib.gsr_eval_view_finish.restype = C.c_int
-    lib.gsr_frame_attributes_backward_acc.argtypes = [C.c_int] * 3 + [fp] * 4 + [C.c_float] + [fp] * 9 + [fp] * 3 + [fp] * 11 + [fp] + [vp]
-    for name in ("gsr_frame_attributes_forward", "gsr_frame_attributes_backward", "gsr_model_activations_forward", "gsr_model_activations_backward", "gsr_frame_attributes_forward_split", "gsr_frame_attributes_backward_split", "gsr_frame_attributes_backward_acc", "gsr_model_activations_backward_acc", "gsr_set_binning_mode", "gsr_set_tuning", "gsr_mark_visible", "gsr_rasterize_forward",
-                 "gsr_rasterize_backward", "gsr_query_state", "gsr_dist2", "gsr_sort_pairs_u64", "gsr_sort_pairs_u32",
-                 "gsr_lbs_forward", "gsr_lbs_backward"):
-        getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes, streamed) in TABLE.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes + [C.c_void_p] * streamed
     return lib
 
 
@@ -365,6 +306,20 @@ def check(rc, what):
     if rc != GSR_OK:
         msg = lib.gsr_last_error()
         raise GsrError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+
+def call(name, device, *args, stream=None):
+    """lib.<name>(*args, stream) on `device`, raising GsrError for a bad status: how every streamed entry point is launched.
+    device None = the current device (no context is entered); stream None = the device's current stream, read now, else a raw
+    handle or a torch.cuda.Stream."""
+    if name not in TABLE:
+        raise AttributeError(f"include/gsr.h declares no function {name}")
+    if not TABLE[name][2]:
+        raise TypeError(f"{name} takes no stream: call lib.{name} directly")
+    stream = torch.cuda.current_stream(device).cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+    with contextlib.nullcontext() if device is None else torch.cuda.device(device):
+        rc = getattr(lib, name)(*args, stream)
+    check(rc, name)
 
 
 def ptr(t):
@@ -402,7 +357,7 @@ def clock_probe(workgroups=1024, fmas=1 << 19, device=None):
     shader cycles per dependent v_fma_f32 of the chain: 8.8 on MI355X, a sanity value that does not move with the clock)."""
     import numpy as np
     out = torch.zeros(2 * workgroups, dtype=torch.int64, device=device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    check(lib.gsr_debug_clock_probe(workgroups, fmas, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "gsr_debug_clock_probe")
+    call("gsr_debug_clock_probe", None, workgroups, fmas, out.data_ptr())
     v = out.cpu().numpy().reshape(workgroups, 2).astype(np.float64)
     ticks, cyc = float(np.median(v[:, 0])), float(np.median(v[:, 1]))
     if ticks <= 0:

@@ -10,7 +10,7 @@ exp, rotation [P,4] = F.normalize, normal [P,3] = x / |x|, occlusion [P,3] = opa
 import torch
 
 from . import gradlink
-from ._lib import check, lib, ptr
+from ._lib import call, ptr
 
 
 class _FrameActivations(torch.autograd.Function):
@@ -24,10 +24,8 @@ class _FrameActivations(torch.autograd.Function):
         raw = [c(opacity_raw), c(albedo_raw), c(scaling_raw), c(rotation_raw), c(normal_raw)]
         new = lambda *s: torch.empty(s, dtype=f32, device=dev)  # noqa: E731
         opacity, albedo, scaling, rotation, normal, occlusion = new(P, 1), new(P, 3), new(P, 3), new(P, 4), new(P, 3), new(P, 3)
-        with torch.cuda.device(dev):
-            check(lib.gsr_model_activations_forward(P, *[ptr(t) for t in raw], ptr(opacity), ptr(albedo), ptr(scaling), ptr(rotation),
-                                                    ptr(normal), ptr(occlusion), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_model_activations_forward")
+        call("gsr_model_activations_forward", dev, P, *[ptr(t) for t in raw], ptr(opacity), ptr(albedo), ptr(scaling), ptr(rotation),
+             ptr(normal), ptr(occlusion))
         ctx.save_for_backward(raw[3], raw[4], opacity, albedo, scaling)
         # (gradlink) this backward runs after the attribute kernel's: it can take that kernel's gradient of the RAW quaternion along
         ctx.link = gradlink.current() if (ctx.needs_input_grad[3] and rotation_raw.is_contiguous()
@@ -48,11 +46,8 @@ class _FrameActivations(torch.autograd.Function):
         acc = None
         if ctx.link is not None and ctx.link.rot_grad is not None:
             acc, ctx.link.rot_grad = ctx.link.rot_grad, None
-        with torch.cuda.device(dev):
-            check(lib.gsr_model_activations_backward_acc(P, ptr(rotation_raw), ptr(normal_raw), ptr(opacity), ptr(albedo),
-                                                         ptr(scaling), *[ptr(g) for g in gs], ptr(d_op), ptr(d_al), ptr(d_sc),
-                                                         ptr(d_ro), ptr(d_no), ptr(acc), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_model_activations_backward")
+        call("gsr_model_activations_backward_acc", dev, P, ptr(rotation_raw), ptr(normal_raw), ptr(opacity), ptr(albedo),
+             ptr(scaling), *[ptr(g) for g in gs], ptr(d_op), ptr(d_al), ptr(d_sc), ptr(d_ro), ptr(d_no), ptr(acc))
         return d_op, d_al, d_sc, d_ro, d_no
 
 

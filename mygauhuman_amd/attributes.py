@@ -13,7 +13,7 @@ import contextlib
 import torch
 
 from . import gradlink
-from ._lib import check, lib, ptr
+from ._lib import call, ptr
 
 # view-parallel compact SH exchange (parallel.ViewParallelRender): while a sink is installed, the backward of the attribute
 # kernel hands (forward colours, dL_dcolours, posed positions) to it -- the three things the rank-one SH gradient of a view is
@@ -47,11 +47,10 @@ class _FrameAttributes(torch.autograd.Function):
         cov3D = torch.empty((P, 6), dtype=f32, device=dev)
         colors = torch.empty((P, 3), dtype=f32, device=dev) if shs is not None else None
         features = torch.empty((P, 18), dtype=f32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_frame_attributes_forward_split(
-                P, int(sh_degree), M, ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), ptr(ins[3]), float(scale_modifier), ptr(ins[4]),
-                ptr(ins[5]), ptr(ins[6]), ptr(ins[7]), ptr(ins[8]), ptr(ins[9]), ptr(rest), ptr(ins[10]), ptr(ins[11]), ptr(cov3D),
-                ptr(colors), ptr(features), torch.cuda.current_stream(dev).cuda_stream), "gsr_frame_attributes_forward")
+        call("gsr_frame_attributes_forward_split", dev,
+             P, int(sh_degree), M, ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), ptr(ins[3]), float(scale_modifier), ptr(ins[4]),
+             ptr(ins[5]), ptr(ins[6]), ptr(ins[7]), ptr(ins[8]), ptr(ins[9]), ptr(rest), ptr(ins[10]), ptr(ins[11]), ptr(cov3D),
+             ptr(colors), ptr(features))
         ctx.has_shs = shs is not None
         ctx.has_rest = rest is not None
         ctx.sink = _SH_SINK if shs is not None else None
@@ -98,13 +97,11 @@ class _FrameAttributes(torch.autograd.Function):
         acc_means = None
         if ctx.link is not None and ctx.link.means_grad is not None:
             acc_means, ctx.link.means_grad = ctx.link.means_grad, None
-        with torch.cuda.device(dev):
-            check(lib.gsr_frame_attributes_backward_acc(
-                P, D, M, ptr(means3D), ptr(transforms), ptr(wn), ptr(scales), mod, ptr(rot_cov), ptr(rot_axis), ptr(albedo),
-                ptr(roughness), ptr(occlusion), ptr(shs), ptr(rest), ptr(campos), ptr(view), ptr(c(g_cov)), ptr(g_colors),
-                ptr(c(g_features)), ptr(d_means), ptr(d_T), ptr(d_wn), ptr(d_scales), ptr(d_rc), ptr(d_ra), ptr(d_alb),
-                ptr(d_rough), ptr(d_occ), ptr(d_shs), ptr(d_rest), ptr(acc_means), torch.cuda.current_stream(dev).cuda_stream),
-                "gsr_frame_attributes_backward")
+        call("gsr_frame_attributes_backward_acc", dev,
+             P, D, M, ptr(means3D), ptr(transforms), ptr(wn), ptr(scales), mod, ptr(rot_cov), ptr(rot_axis), ptr(albedo),
+             ptr(roughness), ptr(occlusion), ptr(shs), ptr(rest), ptr(campos), ptr(view), ptr(c(g_cov)), ptr(g_colors),
+             ptr(c(g_features)), ptr(d_means), ptr(d_T), ptr(d_wn), ptr(d_scales), ptr(d_rc), ptr(d_ra), ptr(d_alb),
+             ptr(d_rough), ptr(d_occ), ptr(d_shs), ptr(d_rest), ptr(acc_means))
         if ctx.park_rot:
             ctx.link.rot_grad, d_rc = d_rc, None
         return (d_means, d_T.view(t_shape), d_wn, d_scales, d_rc, d_ra, d_alb, None if ctx.rough_is_albedo else d_rough, d_occ, d_shs,

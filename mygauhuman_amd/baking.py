@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import call, lib
 
 RES = 10             # grid cells per axis (pc_to_grid(points, 10))
 FACE = 32            # cube face size
@@ -137,10 +137,6 @@ def cube_nearest(cube, dirs):
     return out.reshape(tuple(dirs.shape[:-1]) + (Cn,))
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def grid_cells(points):
     """pc_to_grid on the HIP kernels: (cell id [P] int32, centres [C, 3], grid sizes [3], cell indices [C, 3] int32).  The
     occupied cells are numbered in torch.unique's order, so cell ids equal pc_to_grid's unique_inverse.  Reads C to the host."""
@@ -153,9 +149,8 @@ def grid_cells(points):
     idx = torch.empty((RES ** 3, 3), dtype=torch.int32, device=dev)
     ws = torch.empty((lib.gsr_bake_grid_workspace_bytes(),), dtype=torch.uint8, device=dev)
     n = C.c_int(0)
-    with torch.cuda.device(dev):
-        check(lib.gsr_bake_grid(P, pts.data_ptr(), cell.data_ptr(), centres.data_ptr(), size.data_ptr(), idx.data_ptr(), C.byref(n),
-                                ws.data_ptr(), ws.numel(), _stream(dev)), "gsr_bake_grid")
+    call("gsr_bake_grid", dev, P, pts.data_ptr(), cell.data_ptr(), centres.data_ptr(), size.data_ptr(), idx.data_ptr(), C.byref(n),
+         ws.data_ptr(), ws.numel())
     return cell, centres[:n.value], size, idx[:n.value]
 
 
@@ -175,14 +170,12 @@ def bake_visibility(means3D, scales, rotations, opacity, cell, centres, dirs, wo
     plan = torch.empty((lib.gsr_bake_plan_bytes(P, Cn),), dtype=torch.uint8, device=dev)
     inst = (C.c_ulonglong * 2)()
     stats = (C.c_ulonglong * 4)()
-    with torch.cuda.device(dev):
-        check(lib.gsr_bake_plan(C.byref(scene), plan.data_ptr(), plan.numel(), inst, _stream(dev)), "gsr_bake_plan")
-        budget = WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
-        fixed = lib.gsr_bake_visibility_workspace_bytes(Cn, 0)
-        cap = max(int(inst[1]), min(int(inst[0]), max(0, budget - fixed) // 20))
-        ws = torch.empty((lib.gsr_bake_visibility_workspace_bytes(Cn, cap),), dtype=torch.uint8, device=dev)
-        check(lib.gsr_bake_visibility(C.byref(scene), plan.data_ptr(), vis.data_ptr(), ws.data_ptr(), ws.numel(), stats, _stream(dev)),
-              "gsr_bake_visibility")
+    call("gsr_bake_plan", dev, C.byref(scene), plan.data_ptr(), plan.numel(), inst)
+    budget = WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    fixed = lib.gsr_bake_visibility_workspace_bytes(Cn, 0)
+    cap = max(int(inst[1]), min(int(inst[0]), max(0, budget - fixed) // 20))
+    ws = torch.empty((lib.gsr_bake_visibility_workspace_bytes(Cn, cap),), dtype=torch.uint8, device=dev)
+    call("gsr_bake_visibility", dev, C.byref(scene), plan.data_ptr(), vis.data_ptr(), ws.data_ptr(), ws.numel(), stats)
     LAST_STATS.clear()
     LAST_STATS.update(instances=int(stats[0]), largest_batch=int(stats[1]), batches=int(stats[2]), capacity=int(stats[3]),
                       workspace_bytes=int(ws.numel() + plan.numel()), cells=Cn)
@@ -196,9 +189,7 @@ def expand(cell, normal, dirs, vis, H=ENV_H, W=ENV_W):
     occ = torch.empty((P, H, W, 1), dtype=torch.float32, device=dev)
     n = normal.detach().float().reshape(-1, 3).contiguous()
     d = dirs.detach().float().reshape(-1, 3).contiguous().to(dev)
-    with torch.cuda.device(dev):
-        check(lib.gsr_bake_expand(P, d.shape[0], cell.data_ptr(), n.data_ptr(), d.data_ptr(), vis.data_ptr(), occ.data_ptr(),
-                                  _stream(dev)), "gsr_bake_expand")
+    call("gsr_bake_expand", dev, P, d.shape[0], cell.data_ptr(), n.data_ptr(), d.data_ptr(), vis.data_ptr(), occ.data_ptr())
     return occ
 
 
@@ -212,8 +203,7 @@ def env_occlusion(occlusion, envmap):
     env = envmap.detach().float().reshape(-1).contiguous()
     P = occ.shape[0]
     out = torch.empty((P, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.gsr_bake_env_reduce(P, occ.data_ptr(), env.data_ptr(), out.data_ptr(), _stream(dev)), "gsr_bake_env_reduce")
+    call("gsr_bake_env_reduce", dev, P, occ.data_ptr(), env.data_ptr(), out.data_ptr())
     return out
 
 

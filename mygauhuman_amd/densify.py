@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import covariance
-from ._lib import check, lib
+from ._lib import call
 
 GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "normal", "albedo", "roughness")
 ATTR = dict(xyz="_xyz", f_dc="_features_dc", f_rest="_features_rest", opacity="_opacity", scaling="_scaling",
@@ -109,9 +109,7 @@ def apply_plan(model, plan, reset_stats):
         dst_p = (C.c_void_p * n)(*[outs[i].data_ptr() for i in move])
         w_p = (C.c_int * n)(*[widths[i] for i in move])
         z_p = (C.c_int * n)(*[zero_new[i] for i in move])
-        with torch.cuda.device(dev):
-            check(lib.gsr_gather_rows(n, src_p, dst_p, w_p, z_p, n_out, plan_c.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream), "gsr_gather_rows")
+        call("gsr_gather_rows", dev, n, src_p, dst_p, w_p, z_p, n_out, plan_c.data_ptr())
     # re-register (scene/gaussian_model.py:421-441,463-486)
     by = {(kind, name): o for (kind, name, _, _), o in zip(arrays, outs)}
     for g in GROUPS:

@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
-from .._lib import ALLOC_FN, check, lib, ptr
+from .._lib import ALLOC_FN, call, check, lib, ptr
 from ..fastpath import DeferredStatus
 
 
@@ -22,10 +22,6 @@ def _sh(t):
     if t.numel() and t.dtype == torch.float16:
         return t.contiguous(), _lib.SH_F16
     return _f32c(t, "sh"), _lib.SH_F32
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class _Scratch:
@@ -50,7 +46,7 @@ class _Scratch:
 def _forward_inputs(name, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                     projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug, extra):
     """What both forward bindings share: validation, the output images and, when P > 0, the float32 inputs and the arguments
-    around each entry point's own slots:  entry(<scratch>, *head, <num_rendered | status words>, *tail).
+    around each entry point's own slots:  entry(<scratch>, *head, <num_rendered | status words>, *tail, <stream>).
     Returns ((color, depth, alpha, radii, out_extra | None), head, tail, inputs); head is None when P = 0 (nothing to launch:
     the images are zero, out_extra holds the background).  `inputs` keeps the converted tensors that head / tail point into
     alive: hold it until the call has returned."""
@@ -86,8 +82,7 @@ def _forward_inputs(name, background, means3D, colors, opacity, scales, rotation
             float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix), ptr(campos),
             float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), out_color.data_ptr(), out_depth.data_ptr(),
             out_alpha.data_ptr(), radii.data_ptr(), int(bool(debug)))
-    tail = (ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if out_extra is None else out_extra.data_ptr(), sh_dtype,
-            _stream(dev))
+    tail = (ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if out_extra is None else out_extra.data_ptr(), sh_dtype)
     inputs = (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, extra)
     return images, head, tail, inputs
 
@@ -106,8 +101,10 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     geom, binning, img = _Scratch(dev), _Scratch(dev), _Scratch(dev)
     rendered = C.c_int(0)
     if head is not None:
+        # (not _lib.call: an exception raised inside an allocation callback is reported before the status it caused)
         with torch.cuda.device(dev):
-            rc = lib.gsr_rasterize_forward_ex(geom.cb, None, binning.cb, None, img.cb, None, *head, C.byref(rendered), *tail)
+            rc = lib.gsr_rasterize_forward_ex(geom.cb, None, binning.cb, None, img.cb, None, *head, C.byref(rendered), *tail,
+                                              torch.cuda.current_stream(dev).cuda_stream)
         for s in (geom, binning, img):
             if s.error is not None:
                 raise s.error
@@ -251,9 +248,8 @@ def rasterize_gaussians_async(background, means3D, colors, opacity, scales, rota
     binning = torch.empty((lib.gsr_binning_bytes(cap, W, H),), dtype=u8, device=dev)
     # the (R, flags) words: a device tensor inside a graph capture (examined after replays), pinned host words otherwise
     status = torch.empty((2,), dtype=torch.int32, device=dev) if capturing else AsyncCapacity.status_words(dev)
-    with torch.cuda.device(dev):
-        check(lib.gsr_rasterize_forward_async_ex(geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), *head, status.data_ptr(),
-                                                 *tail), "gsr_rasterize_forward_async_ex")
+    call("gsr_rasterize_forward_async_ex", dev, geom.data_ptr(), binning.data_ptr(), cap, img.data_ptr(), *head, status.data_ptr(),
+         *tail)
     watch = None
     if capturing:
         AsyncCapacity.graph_status.append(status)
@@ -303,8 +299,7 @@ def phase1_loss_forward(spec, color, alpha, out_extra):
     if spec._partials is None or spec._partials.device != dev:
         spec._partials = torch.empty((int(lib.gsr_phase1_loss_partials()),), dtype=torch.float32, device=dev)
     st = spec.struct(_f32c(color, "color"), _f32c(alpha, "alpha"), _f32c(out_extra, "out_extra"), stats)
-    with torch.cuda.device(dev):
-        check(lib.gsr_phase1_loss_forward(W, H, C.byref(st), spec._partials.data_ptr(), _stream(dev)), "gsr_phase1_loss_forward")
+    call("gsr_phase1_loss_forward", dev, W, H, C.byref(st), spec._partials.data_ptr())
     return stats[0], stats
 
 
@@ -368,7 +363,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         # (GSR_FWD_ZERO_ROWS / GSR_BWD_ROWS_ZEROED -- the forward zeroing the gradient rows so that the backward needs no fill
         # kernel -- measured SLOWER in the render() frame: preprocess forward 9.7 -> 19.2 us and backward 18.2 -> 28.7 us against
         # one 5 us fill kernel; the bindings leave both flags off)
-        entry, name, loss = lib.gsr_rasterize_backward_ex, "gsr_rasterize_backward_ex", ()
+        name, loss = "gsr_rasterize_backward_ex", ()
         if phase1 is not None:
             # phase1 = (Phase1Loss, stats [8], upstream dL/dloss (0-dim tensor or None), color [3,H,W], out_extra [18,H,W])
             spec, stats, upstream, p1_color, p1_extra = phase1
@@ -376,20 +371,19 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 raise RuntimeError("the fused phase-1 loss needs the fused multi-feature pass (extra colours)")
             up = None if upstream is None else upstream.detach().to(torch.float32).reshape(1).contiguous()
             st = spec.struct(_f32c(p1_color, "color"), alphas, _f32c(p1_extra, "out_extra"), stats, up)
-            entry, name, loss = lib.gsr_rasterize_backward_phase1_loss, "gsr_rasterize_backward_phase1_loss", (C.byref(st),)
-        with torch.cuda.device(dev):
-            rc = entry(
-                P, int(degree), int(M), int(R), ptr(background), W, H, ptr(means3D), ptr(sh), ptr(colors), ptr(alphas),
-                ptr(scales), float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix),
-                ptr(campos), float(tan_fovx), float(tan_fovy), ptr(radii), geomBuffer.data_ptr(),
-                binningBuffer.data_ptr(), imageBuffer.data_ptr(), ptr(dL_dout_color), ptr(dL_dout_depth),
-                ptr(dL_dout_alpha), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
-                dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-                dL_dsh.data_ptr() if M else None, None if dL_dscales is None else dL_dscales.data_ptr(),
-                None if dL_drotations is None else dL_drotations.data_ptr(), int(bool(debug)),
-                ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if extra is None else extra_ptrs,
-                None if dL_dextra is None else dL_dextra.data_ptr(), sh_dtype, *loss, _stream(dev))
-        check(rc, name)
+            name, loss = "gsr_rasterize_backward_phase1_loss", (C.byref(st),)
+        call(
+            name, dev,
+            P, int(degree), int(M), int(R), ptr(background), W, H, ptr(means3D), ptr(sh), ptr(colors), ptr(alphas),
+            ptr(scales), float(scale_modifier), ptr(rotations), ptr(cov3D_precomp), ptr(viewmatrix), ptr(projmatrix),
+            ptr(campos), float(tan_fovx), float(tan_fovy), ptr(radii), geomBuffer.data_ptr(),
+            binningBuffer.data_ptr(), imageBuffer.data_ptr(), ptr(dL_dout_color), ptr(dL_dout_depth),
+            ptr(dL_dout_alpha), dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(),
+            dL_dcolors.data_ptr(), dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
+            dL_dsh.data_ptr() if M else None, None if dL_dscales is None else dL_dscales.data_ptr(),
+            None if dL_drotations is None else dL_drotations.data_ptr(), int(bool(debug)),
+            ptr(extra), 0 if extra is None else _lib.N_EXTRA, None if extra is None else extra_ptrs,
+            None if dL_dextra is None else dL_dextra.data_ptr(), sh_dtype, *loss)
     if extra is not None:
         return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dextra
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
@@ -403,9 +397,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     present = torch.zeros((P,), dtype=torch.bool, device=means3D.device)
     if P != 0:
         means3D, viewmatrix, projmatrix = _f32c(means3D, "means3D"), _f32c(viewmatrix, "viewmatrix"), _f32c(projmatrix, "projmatrix")
-        with torch.cuda.device(means3D.device):
-            check(lib.gsr_mark_visible(P, ptr(means3D), ptr(viewmatrix), ptr(projmatrix), present.data_ptr(),
-                                       _stream(means3D.device)), "gsr_mark_visible")
+        call("gsr_mark_visible", means3D.device, P, ptr(means3D), ptr(viewmatrix), ptr(projmatrix), present.data_ptr())
     return present
 
 
@@ -421,8 +413,6 @@ def query_state(what, P, R, W, H, geomBuffer, binningBuffer, imageBuffer):
     shape, dt = shapes[what]
     out = torch.zeros(shape, dtype=dt, device=dev)
     if out.numel():
-        with torch.cuda.device(dev):
-            check(lib.gsr_query_state(_lib.Q[what], P, R, W, H, geomBuffer.data_ptr(),
-                                      binningBuffer.data_ptr() if binningBuffer.numel() else None,
-                                      imageBuffer.data_ptr(), out.data_ptr(), _stream(dev)), "gsr_query_state")
+        call("gsr_query_state", dev, _lib.Q[what], P, R, W, H, geomBuffer.data_ptr(),
+             binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(), out.data_ptr())
     return out

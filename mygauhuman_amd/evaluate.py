@@ -20,7 +20,7 @@ import time
 
 import torch
 
-from ._lib import EVAL_FILL, EVAL_FLIP_Z, EVAL_MAX_SLOTS, MASK_F32, MASK_U8, EvalView, check, lib
+from ._lib import EVAL_FILL, EVAL_FLIP_Z, EVAL_MAX_SLOTS, MASK_F32, MASK_U8, EvalView, call, lib
 
 # the eleven images render.py fills under the bound mask (:250-253, :264-270); the ground truths are not filled
 FILL_NAMES = ("render", "render_alpha", "normal", "world_normal", "albedo", "roughness", "render_depth", "render_pbr",
@@ -177,9 +177,7 @@ def finish_view(images, bound_mask, background, metrics=None, metric=("render", 
         ws = torch.empty(int(lib.gsr_eval_workspace_floats(H, W)), device=dev, dtype=torch.float32)
     else:
         v.metric_image = v.metric_gt = -1
-    with torch.cuda.device(dev):
-        check(lib.gsr_eval_view_finish(C.byref(v), ws.data_ptr() if ws is not None else None,
-                                       torch.cuda.current_stream(dev).cuda_stream), "gsr_eval_view_finish")
+    call("gsr_eval_view_finish", dev, C.byref(v), ws.data_ptr() if ws is not None else None)
     return {n: out.get(n, images[n]) for n in names}, u8
 
 

@@ -14,7 +14,7 @@ import dataclasses
 
 import torch
 
-from ._lib import SH_F16, SH_F32, check, lib
+from ._lib import SH_F16, SH_F32, call, lib
 
 ROWS_ZEROED = 2  # GSR_BWD_ROWS_ZEROED (include/gsr.h)
 
@@ -125,32 +125,34 @@ class RasterSession:
         return n
 
     def _stream(self):
+        """The stream of this session's launches: the current one of ITS device, whichever device is current (no context is entered)."""
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def forward(self, params, cam, bg, sh_degree, scale_modifier=1.0):
         """SH + scales/rotations input mode.  Returns (color, depth, alpha, radii) views owned by the session."""
         p = params
         sh_dtype = SH_F16 if p["shs"].dtype == torch.float16 else SH_F32  # fp16 SH storage (extension): widened on load
-        check(lib.gsr_rasterize_forward_async_ex(
+        call(
+            "gsr_rasterize_forward_async_ex", None,
             self.geom.data_ptr(), self.bin.data_ptr(), self.capacity, self.img.data_ptr(), self.P, int(sh_degree), self.M,
             bg.data_ptr(), self.W, self.H, p["means3D"].data_ptr(), p["shs"].data_ptr(), None, p["opacities"].data_ptr(),
             p["scales"].data_ptr(), float(scale_modifier), p["rotations"].data_ptr(), None, cam["viewmatrix"].data_ptr(),
             cam["projmatrix"].data_ptr(), cam["campos"].data_ptr(), float(cam["tanfovx"]), float(cam["tanfovy"]), 0,
             self.color.data_ptr(), self.depth.data_ptr(), self.alpha.data_ptr(), self.radii.data_ptr(), 0,
-            self.status.data_ptr(), None, 0, None, sh_dtype, self._stream()), "gsr_rasterize_forward_async_ex")
+            self.status.data_ptr(), None, 0, None, sh_dtype, stream=self._stream())
         return self.color, self.depth, self.alpha, self.radii
 
     def alpha_mask_loss_backward(self, gt, mask, lambda_alpha=0.1):
-        check(lib.gsr_alpha_mask_loss_backward(self.W, self.H, self.color.data_ptr(), self.alpha.data_ptr(), gt.data_ptr(),
-                                               mask.data_ptr(), float(lambda_alpha), self.dL_dcolor.data_ptr(),
-                                               self.dL_dalpha.data_ptr(), self._stream()), "gsr_alpha_mask_loss_backward")
+        call("gsr_alpha_mask_loss_backward", None, self.W, self.H, self.color.data_ptr(), self.alpha.data_ptr(), gt.data_ptr(),
+             mask.data_ptr(), float(lambda_alpha), self.dL_dcolor.data_ptr(), self.dL_dalpha.data_ptr(), stream=self._stream())
         return self.dL_dcolor, self.dL_dalpha
 
     def backward(self, params, cam, bg, sh_degree, dL_dcolor, dL_ddepth, dL_dalpha, out, scale_modifier=1.0):
         """out: dict with means3D / sh / opacity / scales / rotations gradient tensors (written in place)."""
         p = params
         sh_dtype = SH_F16 if p["shs"].dtype == torch.float16 else SH_F32
-        check(lib.gsr_rasterize_backward_ex(
+        call(
+            "gsr_rasterize_backward_ex", None,
             self.P, int(sh_degree), self.M, self.capacity, bg.data_ptr(), self.W, self.H, p["means3D"].data_ptr(),
             p["shs"].data_ptr(), None, self.alpha.data_ptr(), p["scales"].data_ptr(), float(scale_modifier),
             p["rotations"].data_ptr(), None, cam["viewmatrix"].data_ptr(), cam["projmatrix"].data_ptr(),
@@ -158,8 +160,8 @@ class RasterSession:
             self.geom.data_ptr(), self.bin.data_ptr(), self.img.data_ptr(), dL_dcolor.data_ptr(), dL_ddepth.data_ptr(),
             dL_dalpha.data_ptr(), self.dL_dmean2D.data_ptr(), self.dL_dconic.data_ptr(), out["opacity"].data_ptr(),
             self.dL_dcolors.data_ptr(), out["means3D"].data_ptr(), self.dL_dcov3D.data_ptr(), out["sh"].data_ptr(),
-            out["scales"].data_ptr(), out["rotations"].data_ptr(), ROWS_ZEROED, None, 0, None, None, sh_dtype, self._stream()),
-            "gsr_rasterize_backward_ex")
+            out["scales"].data_ptr(), out["rotations"].data_ptr(), ROWS_ZEROED, None, 0, None, None, sh_dtype,
+            stream=self._stream())
 
     def backward_alpha_mask_loss(self, params, cam, bg, sh_degree, gt, mask, lambda_alpha, out, scale_modifier=1.0):
         """backward() of the loss  mean|color - gt| + lambda_alpha * mean (alpha - mask)^2  of the last forward, with the loss
@@ -167,7 +169,8 @@ class RasterSession:
         for bit, as alpha_mask_loss_backward() + backward()."""
         p = params
         sh_dtype = SH_F16 if p["shs"].dtype == torch.float16 else SH_F32
-        check(lib.gsr_rasterize_backward_alpha_mask_loss(
+        call(
+            "gsr_rasterize_backward_alpha_mask_loss", None,
             self.P, int(sh_degree), self.M, self.capacity, bg.data_ptr(), self.W, self.H, p["means3D"].data_ptr(),
             p["shs"].data_ptr(), None, self.alpha.data_ptr(), p["scales"].data_ptr(), float(scale_modifier),
             p["rotations"].data_ptr(), None, cam["viewmatrix"].data_ptr(), cam["projmatrix"].data_ptr(),
@@ -175,8 +178,7 @@ class RasterSession:
             self.geom.data_ptr(), self.bin.data_ptr(), self.img.data_ptr(), self.color.data_ptr(), gt.data_ptr(), mask.data_ptr(),
             float(lambda_alpha), self.dL_dmean2D.data_ptr(), self.dL_dconic.data_ptr(), out["opacity"].data_ptr(),
             self.dL_dcolors.data_ptr(), out["means3D"].data_ptr(), self.dL_dcov3D.data_ptr(), out["sh"].data_ptr(),
-            out["scales"].data_ptr(), out["rotations"].data_ptr(), ROWS_ZEROED, sh_dtype, self._stream()),
-            "gsr_rasterize_backward_alpha_mask_loss")
+            out["scales"].data_ptr(), out["rotations"].data_ptr(), ROWS_ZEROED, sh_dtype, stream=self._stream())
 
     # `status` may be a device tensor (default) or a pinned host tensor that the kernels write directly (ViewParallelStep)
     def _status_word(self, k):

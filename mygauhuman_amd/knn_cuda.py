@@ -12,7 +12,7 @@ package cannot be installed here: parity unpinned, semantics as stated.  No CPU 
 """
 import torch
 
-from ._lib import check, lib, ptr
+from ._lib import call, lib, ptr
 
 
 def _is_same(a, b):
@@ -29,9 +29,7 @@ def knn_self(points, k):
     dist = torch.empty((P, k), dtype=torch.float32, device=dev)
     if P:
         ws = torch.empty((lib.gsr_dist2_workspace_bytes(P),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_knn_self(P, ptr(pts), int(k), ptr(idx), ptr(dist), ptr(ws), ws.numel(),
-                                   torch.cuda.current_stream(dev).cuda_stream), "gsr_knn_self")
+        call("gsr_knn_self", dev, P, ptr(pts), int(k), ptr(idx), ptr(dist), ptr(ws), ws.numel())
     return dist, idx
 
 
@@ -45,9 +43,7 @@ def knn_nearest(ref, query):
     dist = torch.empty((M,), dtype=torch.float32, device=dev)
     if M:
         ws = torch.empty((lib.gsr_lbs_workspace_bytes(N),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_knn_nearest(M, ptr(q), N, ptr(r), ptr(idx), ptr(dist), ptr(ws), ws.numel(),
-                                      torch.cuda.current_stream(dev).cuda_stream), "gsr_knn_nearest")
+        call("gsr_knn_nearest", dev, M, ptr(q), N, ptr(r), ptr(idx), ptr(dist), ptr(ws), ws.numel())
     return dist, idx
 
 

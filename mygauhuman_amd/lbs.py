@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import check, lib, ptr
+from ._lib import call, lib, ptr
 
 
 def batch_rodrigues(rot_vecs):
@@ -41,9 +41,7 @@ class _RowGemv(torch.autograd.Function):
         dev = mat.device
         m, v = mat.detach().contiguous().float(), vec.detach().contiguous().float()
         out = torch.empty((m.shape[0],), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_gemv_rows(m.shape[0], m.shape[1], ptr(m), ptr(v), ptr(out), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_gemv_rows")
+        call("gsr_gemv_rows", dev, m.shape[0], m.shape[1], ptr(m), ptr(v), ptr(out))
         ctx.save_for_backward(m)
         ctx.vshape = vec.shape
         return out
@@ -53,9 +51,7 @@ class _RowGemv(torch.autograd.Function):
         (m,) = ctx.saved_tensors
         dv = torch.empty((m.shape[1],), dtype=torch.float32, device=m.device)
         g = g.contiguous().float()
-        with torch.cuda.device(m.device):
-            check(lib.gsr_gemv_rows_t(m.shape[0], m.shape[1], ptr(m), ptr(g), ptr(dv), torch.cuda.current_stream(m.device).cuda_stream),
-                  "gsr_gemv_rows_t")
+        call("gsr_gemv_rows_t", m.device, m.shape[0], m.shape[1], ptr(m), ptr(g), ptr(dv))
         return None, dv.view(ctx.vshape)
 
 
@@ -157,9 +153,7 @@ class _SmplPose(torch.autograd.Function):
         par = (C.c_int * J)(*parents)
         rot = torch.empty((J, 3, 3), dtype=f32, device=dev)
         A = torch.empty((J, 4, 4), dtype=f32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_body_pose_forward(J, ptr(poses_c), ptr(cr), ptr(j), par, ptr(rot), ptr(A),
-                                            torch.cuda.current_stream(dev).cuda_stream), "gsr_body_pose_forward")
+        call("gsr_body_pose_forward", dev, J, ptr(poses_c), ptr(cr), ptr(j), par, ptr(rot), ptr(A))
         ctx.has_cr = cr is not None
         ctx.save_for_backward(*([poses_c, j] + ([cr] if cr is not None else [])))
         ctx.meta = (parents, poses.shape, None if correct_Rs is None else correct_Rs.shape, joints.shape)
@@ -180,9 +174,7 @@ class _SmplPose(torch.autograd.Function):
         d_j = torch.empty((J, 3), dtype=f32, device=dev) if need_j else None
         g_A = torch.zeros((J, 4, 4), dtype=f32, device=dev) if g_A is None else g_A.contiguous().float()
         g_rot = None if g_rot is None else g_rot.contiguous().float()
-        with torch.cuda.device(dev):
-            check(lib.gsr_body_pose_backward(J, ptr(poses), ptr(cr), ptr(j), par, ptr(g_A), ptr(g_rot), ptr(d_p), ptr(d_c), ptr(d_j),
-                                             torch.cuda.current_stream(dev).cuda_stream), "gsr_body_pose_backward")
+        call("gsr_body_pose_backward", dev, J, ptr(poses), ptr(cr), ptr(j), par, ptr(g_A), ptr(g_rot), ptr(d_p), ptr(d_c), ptr(d_j))
         return (None if d_p is None else d_p.view(p_shape), None if d_c is None else d_c.view(c_shape),
                 None if d_j is None else d_j.view(j_shape), None)
 
@@ -294,24 +286,21 @@ class _LBSDeform(torch.autograd.Function):
         args = (J, P, V, ptr(query_c), ptr(normals_c), ptr(sv), ptr(w), ptr(loff), ptr(A_big_c), ptr(A_pose_c), ptr(ob), ptr(os_),
                 ptr(op), ptr(R_c), ptr(Th_c), ptr(vert_ids), ptr(bweights), ptr(smpl_pts), ptr(world_pts), ptr(transforms),
                 ptr(translation), ptr(world_normals))
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if NEAREST_VERTEX_SEARCH == "grid":
-                if sv.data_ptr() == smpl_verts.data_ptr():   # the caller's own storage (no conversion copy): remember its grid
-                    ws, built = _GRIDS.get(smpl_verts)
-                else:
-                    ws, built = torch.empty((lib.gsr_lbs_workspace_bytes(V),), dtype=torch.uint8, device=dev), False
-                if NN_TEMPORAL_CACHE and sv.data_ptr() == smpl_verts.data_ptr():
-                    # frame-to-frame: a point that has not left the ball its entry vouches for keeps its vertex without a search
-                    if not built:
-                        check(lib.gsr_lbs_grid_build(V, ptr(sv), ptr(ws), ws.numel(), stream), "gsr_lbs_grid_build")
-                    nn, valid = _GRIDS.nn_cache(smpl_verts, P)
-                    check(lib.gsr_lbs_forward_cached_nj(*args, ptr(ws), ws.numel(), ptr(nn), nn.numel(), int(valid), stream),
-                          "gsr_lbs_forward_cached_nj")
-                else:
-                    check(lib.gsr_lbs_forward_grid_nj(*args, ptr(ws), ws.numel(), int(built), stream), "gsr_lbs_forward_grid_nj")
+        if NEAREST_VERTEX_SEARCH == "grid":
+            if sv.data_ptr() == smpl_verts.data_ptr():   # the caller's own storage (no conversion copy): remember its grid
+                ws, built = _GRIDS.get(smpl_verts)
             else:
-                check(lib.gsr_lbs_forward_nj(*args, stream), "gsr_lbs_forward_nj")
+                ws, built = torch.empty((lib.gsr_lbs_workspace_bytes(V),), dtype=torch.uint8, device=dev), False
+            if NN_TEMPORAL_CACHE and sv.data_ptr() == smpl_verts.data_ptr():
+                # frame-to-frame: a point that has not left the ball its entry vouches for keeps its vertex without a search
+                if not built:
+                    call("gsr_lbs_grid_build", dev, V, ptr(sv), ptr(ws), ws.numel())
+                nn, valid = _GRIDS.nn_cache(smpl_verts, P)
+                call("gsr_lbs_forward_cached_nj", dev, *args, ptr(ws), ws.numel(), ptr(nn), nn.numel(), int(valid))
+            else:
+                call("gsr_lbs_forward_grid_nj", dev, *args, ptr(ws), ws.numel(), int(built))
+        else:
+            call("gsr_lbs_forward_nj", dev, *args)
         ctx.save_for_backward(query_c, normals_c, loff, A_big_c, A_pose_c, ob, os_, op, R_c, vert_ids, w)
         ctx.shapes = (A_pose.shape, off_pose.shape, V)
         e = torch.empty(0, device=dev)
@@ -339,11 +328,9 @@ class _LBSDeform(torch.autograd.Function):
         d_A = torch.zeros((J, 16), dtype=f32, device=dev) if need_A else None
         partials = torch.empty((lib.gsr_lbs_backward_workgroups(P), J * 12), dtype=f32, device=dev) if need_A else None
         d_off = torch.zeros((V, 3), dtype=f32, device=dev) if need_off else None
-        with torch.cuda.device(dev):
-            check(lib.gsr_lbs_backward_nj(J, P, V, ptr(query), ptr(normals), ptr(vert_ids), ptr(w), ptr(loff), ptr(A_big), ptr(A_pose),
-                                       ptr(ob), ptr(os_), ptr(op), ptr(R), ptr(g_world), ptr(g_transforms), ptr(g_normals),
-                                       ptr(d_query), ptr(d_normals), ptr(d_loff), ptr(d_A), ptr(d_off), ptr(partials),
-                                       torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_backward_nj")
+        call("gsr_lbs_backward_nj", dev, J, P, V, ptr(query), ptr(normals), ptr(vert_ids), ptr(w), ptr(loff), ptr(A_big), ptr(A_pose),
+             ptr(ob), ptr(os_), ptr(op), ptr(R), ptr(g_world), ptr(g_transforms), ptr(g_normals),
+             ptr(d_query), ptr(d_normals), ptr(d_loff), ptr(d_A), ptr(d_off), ptr(partials))
         if need_A:  # per-workgroup sums -> rows 0..2 of the J 4x4 gradients (row 3 of A is constant)
             d_A.view(J, 4, 4)[:, :3, :] = partials.sum(0).view(J, 3, 4)
         return (d_query, d_normals, d_loff, None, None if d_A is None else d_A.view(A_shape), None, None,

@@ -13,7 +13,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import MASK_F32, MASK_U8, SSIM_CROP_MAX_GROUPS, SsimCrop, check, lib, ptr
+from ._lib import MASK_F32, MASK_U8, SSIM_CROP_MAX_GROUPS, SsimCrop, call, lib, ptr
 
 
 def l1_loss(network_output, gt):
@@ -34,9 +34,7 @@ class _SsimMap(torch.autograd.Function):
         out = torch.empty_like(a)
         need = ctx.needs_input_grad[0]
         dA, dB, dC = (torch.empty_like(a) for _ in range(3)) if need else (None, None, None)
-        with torch.cuda.device(dev):
-            check(lib.gsr_ssim_forward(planes, H, W, ptr(a), ptr(b), ptr(out), ptr(dA), ptr(dB), ptr(dC),
-                                       torch.cuda.current_stream(dev).cuda_stream), "gsr_ssim_forward")
+        call("gsr_ssim_forward", dev, planes, H, W, ptr(a), ptr(b), ptr(out), ptr(dA), ptr(dB), ptr(dC))
         if need:
             ctx.save_for_backward(a, b, dA, dB, dC)
         ctx.dims = (planes, H, W)
@@ -48,9 +46,7 @@ class _SsimMap(torch.autograd.Function):
         planes, H, W = ctx.dims
         g = g.contiguous().float()
         out = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            check(lib.gsr_ssim_backward(planes, H, W, ptr(a), ptr(b), ptr(g), 0.0, ptr(dA), ptr(dB), ptr(dC), ptr(out),
-                                        torch.cuda.current_stream(a.device).cuda_stream), "gsr_ssim_backward")
+        call("gsr_ssim_backward", a.device, planes, H, W, ptr(a), ptr(b), ptr(g), 0.0, ptr(dA), ptr(dB), ptr(dC), ptr(out))
         return out, None
 
 
@@ -92,9 +88,8 @@ def bounding_rect(mask, out=None):
         raise ValueError("bounding_rect: out must be a contiguous int32 [4] tensor on the mask's device")
     ws = torch.empty(int(lib.gsr_bounding_rect_workspace_ints()), device=dev, dtype=torch.int32)
     H, W = m.shape
-    with torch.cuda.device(dev):
-        check(lib.gsr_bounding_rect(H, W, m.data_ptr(), MASK_F32 if m.dtype == torch.float32 else MASK_U8, out.data_ptr(),
-                                    ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gsr_bounding_rect")
+    call("gsr_bounding_rect", dev, H, W, m.data_ptr(), MASK_F32 if m.dtype == torch.float32 else MASK_U8, out.data_ptr(),
+         ws.data_ptr())
     return out
 
 
@@ -124,9 +119,7 @@ class _SsimCrop(torch.autograd.Function):
         s = _crop_struct(rect, a, b, maps)
         for g in range(n):
             s.value[g] = values[g].data_ptr()
-        with torch.cuda.device(dev):
-            check(lib.gsr_ssim_crop_forward(C.byref(s), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_ssim_crop_forward")
+        call("gsr_ssim_crop_forward", dev, C.byref(s), ws.data_ptr())
         ctx.n, ctx.need = n, need
         ctx.save_for_backward(rect, *a, *b, *[m for t in maps if t is not None for m in t])
         return tuple(values)
@@ -146,8 +139,7 @@ class _SsimCrop(torch.autograd.Function):
             for g in range(n):
                 s.upstream[g] = ups[g].data_ptr()
                 s.d_img1[g] = ptr(outs[g])
-            with torch.cuda.device(dev):
-                check(lib.gsr_ssim_crop_backward(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "gsr_ssim_crop_backward")
+            call("gsr_ssim_crop_backward", dev, C.byref(s))
         return (None, None, *outs, *([None] * n))
 
 

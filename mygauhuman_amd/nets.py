@@ -20,7 +20,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import check, lib, ptr
+from ._lib import call, check, lib, ptr
 
 _OCTAVES = 10
 FUSED_BONE_COUNTS = (24, 55)   # the output widths csrc/mlp.hip is compiled for (one or two 32-row tiles)
@@ -111,17 +111,13 @@ def _pack(nb, params, dev, out=None):
     n = int(lib.gsr_lbs_offset_mlp_packed_floats_nb(nb))
     packed = torch.empty(n, dtype=torch.float32, device=dev) if out is None or out.numel() != n else out
     mk = lambda xs: (C.c_void_p * 5)(*[x.data_ptr() for x in xs])  # noqa: E731  (host arrays of device pointers)
-    with torch.cuda.device(dev):
-        check(lib.gsr_lbs_offset_mlp_pack_nb(nb, mk(params[0::2]), mk(params[1::2]), ptr(packed), torch.cuda.current_stream(dev).cuda_stream),
-              "gsr_lbs_offset_mlp_pack_nb")
+    call("gsr_lbs_offset_mlp_pack_nb", dev, nb, mk(params[0::2]), mk(params[1::2]), ptr(packed))
     return packed
 
 
 def _forward_fused(nb, x, packed):
     out = torch.empty((x.shape[0], nb), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib.gsr_lbs_offset_mlp_forward_nb(nb, x.shape[0], ptr(x), ptr(packed), ptr(out), torch.cuda.current_stream(x.device).cuda_stream),
-              "gsr_lbs_offset_mlp_forward_nb")
+    call("gsr_lbs_offset_mlp_forward_nb", x.device, nb, x.shape[0], ptr(x), ptr(packed), ptr(out))
     return out
 
 
@@ -155,9 +151,7 @@ class _FusedOffsetNet(torch.autograd.Function):
         nb = ctx.nb
         ws = torch.empty(int(lib.gsr_lbs_offset_mlp_backward_workspace_floats_nb(nb, P)), dtype=torch.float32, device=dev)
         mk = lambda xs: (C.c_void_p * 5)(*[t.data_ptr() for t in xs])  # noqa: E731
-        with torch.cuda.device(dev):
-            check(lib.gsr_lbs_offset_mlp_backward_nb(nb, P, ptr(x), ptr(packed), ptr(g), ptr(ws), mk(grads[0::2]), mk(grads[1::2]),
-                                                     torch.cuda.current_stream(dev).cuda_stream), "gsr_lbs_offset_mlp_backward_nb")
+        call("gsr_lbs_offset_mlp_backward_nb", dev, nb, P, ptr(x), ptr(packed), ptr(g), ptr(ws), mk(grads[0::2]), mk(grads[1::2]))
         return (None, None, *grads)
 
 

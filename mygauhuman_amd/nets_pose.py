@@ -26,7 +26,7 @@ import math
 import torch
 from torch import nn
 
-from ._lib import check, lib
+from ._lib import call
 
 FUSED_JOINTS = (24, 55)     # the joint counts csrc/pose_refiner.hip is compiled for
 FUSED_WIDTH = 128
@@ -131,10 +131,8 @@ class _FusedPoseRefiner(torch.autograd.Function):
         ps = [t.detach() for t in (w0, b0, w2, b2, w4, b4)]
         B, dev = x.shape[0], x.device
         Rs = torch.empty((B, J - 1, 3, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.gsr_pose_refiner_forward(J, B, FUSED_WIDTH, x.data_ptr(), x.stride(0), x.stride(1), _ptrs(ps[0::2]),
-                                               _ptrs(ps[1::2]), Rs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_pose_refiner_forward")
+        call("gsr_pose_refiner_forward", dev, J, B, FUSED_WIDTH, x.data_ptr(), x.stride(0), x.stride(1), _ptrs(ps[0::2]),
+             _ptrs(ps[1::2]), Rs.data_ptr())
         ctx.save_for_backward(x, *ps)
         ctx.J = J
         return Rs
@@ -146,9 +144,6 @@ class _FusedPoseRefiner(torch.autograd.Function):
         g = g.contiguous()
         grads = [torch.empty_like(p) for p in ps]
         dx = torch.empty((B, x.shape[1]), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dev):
-            check(lib.gsr_pose_refiner_backward(ctx.J, B, FUSED_WIDTH, x.data_ptr(), x.stride(0), x.stride(1), _ptrs(ps[0::2]),
-                                                _ptrs(ps[1::2]), g.data_ptr(), _ptrs(grads[0::2]), _ptrs(grads[1::2]),
-                                                None if dx is None else dx.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  "gsr_pose_refiner_backward")
+        call("gsr_pose_refiner_backward", dev, ctx.J, B, FUSED_WIDTH, x.data_ptr(), x.stride(0), x.stride(1), _ptrs(ps[0::2]),
+             _ptrs(ps[1::2]), g.data_ptr(), _ptrs(grads[0::2]), _ptrs(grads[1::2]), None if dx is None else dx.data_ptr())
         return (dx, None, *[gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[2:])])

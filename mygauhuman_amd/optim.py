@@ -25,7 +25,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import call
 
 MAX_ARRAYS = _lib.ADAM_MAX_ARRAYS   # tensors per launch (include/gsr.h: GSR_ADAM_MAX_ARRAYS)
 MAX_GROUPS = _lib.ADAM_MAX_GROUPS   # parameter groups per launch
@@ -112,8 +112,7 @@ def update_stats(model, viewspace_point_tensor, update_filter, radii, debug=Fals
     densify_and_prune runs between the statistics and the step."""
     st, keep = _stats_block(model, viewspace_point_tensor, update_filter, radii)
     dev = keep[3].device
-    with torch.cuda.device(dev):
-        check(lib.gsr_stats_update(C.byref(st), int(debug), torch.cuda.current_stream(dev).cuda_stream), "gsr_stats_update")
+    call("gsr_stats_update", dev, C.byref(st), int(debug))
 
 
 class FusedAdam(torch.optim.Adam):
@@ -296,10 +295,7 @@ class FusedAdam(torch.optim.Adam):
             st_block, keep = _stats_block(model, vpt, update_filter, radii)
         if not items:
             if st_block is not None:
-                dev = keep[3].device
-                with torch.cuda.device(dev):
-                    check(lib.gsr_stats_update(C.byref(st_block), int(self._debug), torch.cuda.current_stream(dev).cuda_stream),
-                          "gsr_stats_update")
+                call("gsr_stats_update", keep[3].device, C.byref(st_block), int(self._debug))
             return loss
         dev = items[0][0].device
         key = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
@@ -314,16 +310,13 @@ class FusedAdam(torch.optim.Adam):
             raise RuntimeError("FusedAdam.step under stream capture reads its learning rates from lr_tensor(): call sync_lr() once "
                                "before the capture (and before every replay)")
         lr_ptr = self._lr_table.data_ptr() if capturing else None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for n, (arr, grp, gids) in enumerate(self._launches):
-                for k, gi in enumerate(gids):
-                    group = self.param_groups[gi]
-                    b1, b2 = group["betas"]
-                    grp[k] = _lib.AdamGroup(float(b1), float(b2), float(group["lr"]), float(group["eps"]),
-                                            float(group.get("clamp_min", -math.inf)), gi)
-                last = n == len(self._launches) - 1
-                check(lib.gsr_adam_step(len(arr), arr, len(grp), grp, lr_ptr, self._steps.data_ptr(),
-                                        C.byref(st_block) if (st_block is not None and last) else None, int(self._debug), stream),
-                      "gsr_adam_step")
+        for n, (arr, grp, gids) in enumerate(self._launches):
+            for k, gi in enumerate(gids):
+                group = self.param_groups[gi]
+                b1, b2 = group["betas"]
+                grp[k] = _lib.AdamGroup(float(b1), float(b2), float(group["lr"]), float(group["eps"]),
+                                        float(group.get("clamp_min", -math.inf)), gi)
+            last = n == len(self._launches) - 1
+            call("gsr_adam_step", dev, len(arr), arr, len(grp), grp, lr_ptr, self._steps.data_ptr(),
+                 C.byref(st_block) if (st_block is not None and last) else None, int(self._debug))
         return loss

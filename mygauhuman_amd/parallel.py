@@ -19,7 +19,7 @@ from collections import OrderedDict
 import torch
 import torch.distributed as dist
 
-from ._lib import check, lib
+from ._lib import call
 from .launch import free_port, spawn_ranks  # noqa: F401  (re-exported)
 
 
@@ -237,17 +237,14 @@ class CompactShExchange:
 
     def pack(self, session, campos):
         """Static path: fill this rank's block from the session's last backward (its raw dL_dcolor + the forward's clamp bits)."""
-        dev = self.mine.device
-        check(lib.gsr_sh_view_pack(self.P, session.geom.data_ptr(), session.dL_dcolors.data_ptr(), self.mine.data_ptr(),
-                                   torch.cuda.current_stream(dev).cuda_stream), "gsr_sh_view_pack")
+        call("gsr_sh_view_pack", self.mine.device, self.P, session.geom.data_ptr(), session.dL_dcolors.data_ptr(),
+             self.mine.data_ptr())
         self.mine[self.P * 3:self.P * 3 + 3].copy_(campos.reshape(3))
 
     def pack_posed(self, colors, g_colors, means_view, campos, radii=None):
         """Articulated path: masked dL_dRGB, this view's posed positions and camera position in one launch (+ the radii)."""
-        dev = self.mine.device
-        check(lib.gsr_sh_view_pack_posed(self.P, colors.data_ptr(), g_colors.data_ptr(), means_view.data_ptr(), campos.data_ptr(),
-                                         self.mine.data_ptr(), self.means_off, self.cam_off,
-                                         torch.cuda.current_stream(dev).cuda_stream), "gsr_sh_view_pack_posed")
+        call("gsr_sh_view_pack_posed", self.mine.device, self.P, colors.data_ptr(), g_colors.data_ptr(), means_view.data_ptr(),
+             campos.data_ptr(), self.mine.data_ptr(), self.means_off, self.cam_off)
         if radii is not None:
             self.mine[self.radii_off:self.radii_off + self.P].copy_(radii)  # int32 -> float32 (exact below 2^24 pixels)
 
@@ -317,14 +314,12 @@ class CompactShExchange:
         n_views = self.world if n_views is None else int(n_views)
         scale = 1.0 if dev_scale is not None else 1.0 / n_views
         ds = None if dev_scale is None else dev_scale.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
         if self.posed:
-            check(lib.gsr_sh_grad_from_views_posed(self.P, int(sh_degree), n_views, self.gathered.data_ptr(), self.stride,
-                                                   self.means_off, self.cam_off, scale, ds, self.grad_dc.data_ptr(),
-                                                   self.grad_rest.data_ptr(), stream), "gsr_sh_grad_from_views_posed")
+            call("gsr_sh_grad_from_views_posed", dev, self.P, int(sh_degree), n_views, self.gathered.data_ptr(), self.stride,
+                 self.means_off, self.cam_off, scale, ds, self.grad_dc.data_ptr(), self.grad_rest.data_ptr())
             return self.grad_dc, self.grad_rest
-        check(lib.gsr_sh_grad_from_views(self.P, int(sh_degree), self.M, n_views, means3D.data_ptr(), self.gathered.data_ptr(),
-                                         self.stride, scale, ds, self.grad.data_ptr(), stream), "gsr_sh_grad_from_views")
+        call("gsr_sh_grad_from_views", dev, self.P, int(sh_degree), self.M, n_views, means3D.data_ptr(), self.gathered.data_ptr(),
+             self.stride, scale, ds, self.grad.data_ptr())
         return self.grad
 
     def max_radii(self, n_views=None):
@@ -411,10 +406,8 @@ class ViewParallelStep:
 
     # ---- deferred overflow checks
     def _status(self, phase, report=None):
-        dev = self._scale.device
-        check(lib.gsr_step_status(phase, self.session.status.data_ptr(), self.bucket["overflow"].data_ptr(), 1.0 / self.world,
-                                  self._scale.data_ptr(), None if report is None else report.data_ptr(),
-                                  torch.cuda.current_stream(dev).cuda_stream), "gsr_step_status")
+        call("gsr_step_status", self._scale.device, phase, self.session.status.data_ptr(), self.bucket["overflow"].data_ptr(),
+             1.0 / self.world, self._scale.data_ptr(), None if report is None else report.data_ptr())
 
     def _decide(self, step, words):
         if self.world > 1:   # [ranks that overflowed, R, own flag], written by gsr_step_finish after the all-reduce
@@ -471,9 +464,8 @@ class ViewParallelStep:
             self.timer.end(dev)
             # scale = 1 / world, or 0 if any rank overflowed (a skipped step is skipped by every replica), the whole bucket times
             # scale and the report words: one launch (gsr_step_finish)
-            check(lib.gsr_step_finish(s.status.data_ptr(), b.flat.data_ptr(), b.flat.numel(), b.slices["overflow"][0],
-                                      (1.0 / self.world) if reduce else 1.0, self._scale.data_ptr(), host.data_ptr(),
-                                      torch.cuda.current_stream(dev).cuda_stream), "gsr_step_finish")
+            call("gsr_step_finish", dev, s.status.data_ptr(), b.flat.data_ptr(), b.flat.numel(), b.slices["overflow"][0],
+                 (1.0 / self.world) if reduce else 1.0, self._scale.data_ptr(), host.data_ptr())
             if reduce and self.compact is not None:
                 self.compact.reconstruct(self.p["means3D"], self.deg, self._scale)
         # (a single process needs no scaling: its own overflowed step has exactly zero gradients already)
@@ -708,9 +700,8 @@ class ViewParallelRender:
             if self.compact is not None:
                 self.compact.local()
         # scale = 1 / n_views (0 if any rank overflowed), the bucket times scale, the report words: one launch
-        check(lib.gsr_step_finish(None, b.flat.data_ptr(), b.flat.numel(), b.slices["overflow"][0], 1.0 / n_views,
-                                  self._scale.data_ptr(), host.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-              "gsr_step_finish")
+        call("gsr_step_finish", dev, None, b.flat.data_ptr(), b.flat.numel(), b.slices["overflow"][0], 1.0 / n_views,
+             self._scale.data_ptr(), host.data_ptr())
         if n_views > 1:  # the statistics are SUMS over the views, not means
             b["stat_grad_norm"].mul_(float(n_views))
             b["stat_visible"].mul_(float(n_views))

@@ -5,17 +5,13 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .._lib import PBR_MAX_LEVELS, PbrShade, PbrTexture, check, lib, ptr
+from .._lib import PBR_MAX_LEVELS, PbrShade, PbrTexture, call, ptr
 
 
 def _dev(t, what):
     if not t.is_cuda:
         raise RuntimeError(f"{what}: tensors must live on a HIP device (no CPU path)")
     return t.detach().contiguous().float()
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def make_texture(levels, cube, grads=None):
@@ -42,8 +38,7 @@ class TextureFn(torch.autograd.Function):
         n = c.shape[0]
         out = torch.empty(n, lv[0].shape[-1], device=c.device, dtype=torch.float32)
         tex = make_texture(lv, cube)
-        with torch.cuda.device(c.device):
-            check(lib.gsr_pbr_texture_forward(C.byref(tex), n, ptr(c), ptr(b), ptr(out), _stream(c)), "gsr_pbr_texture_forward")
+        call("gsr_pbr_texture_forward", c.device, C.byref(tex), n, ptr(c), ptr(b), ptr(out))
         ctx.cube = cube
         ctx.save_for_backward(c, b, *lv)
         return out
@@ -57,9 +52,7 @@ class TextureFn(torch.autograd.Function):
         db = torch.empty_like(b) if (b is not None and need[2]) else None
         g = g.contiguous().float()
         tex = make_texture(lv, ctx.cube, grads)
-        with torch.cuda.device(c.device):
-            check(lib.gsr_pbr_texture_backward(C.byref(tex), c.shape[0], ptr(c), ptr(b), ptr(g), ptr(dc), ptr(db), _stream(c)),
-                  "gsr_pbr_texture_backward")
+        call("gsr_pbr_texture_backward", c.device, C.byref(tex), c.shape[0], ptr(c), ptr(b), ptr(g), ptr(dc), ptr(db))
         return (None, dc, db, *grads)
 
 
@@ -70,8 +63,7 @@ class CubeMipFn(torch.autograd.Function):
         x = _dev(cube, "cubemap_mip")
         n, ch = x.shape[1], x.shape[-1]
         out = torch.empty(6, n // 2, n // 2, ch, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            check(lib.gsr_pbr_cube_mip_forward(n, ch, ptr(x), ptr(out), _stream(x)), "gsr_pbr_cube_mip_forward")
+        call("gsr_pbr_cube_mip_forward", x.device, n, ch, ptr(x), ptr(out))
         return out
 
     @staticmethod
@@ -79,8 +71,7 @@ class CubeMipFn(torch.autograd.Function):
         g = g.contiguous().float()
         n, ch = g.shape[1] * 2, g.shape[-1]
         out = torch.empty(6, n, n, ch, device=g.device, dtype=torch.float32)
-        with torch.cuda.device(g.device):
-            check(lib.gsr_pbr_cube_mip_backward(n, ch, ptr(g), ptr(out), _stream(g)), "gsr_pbr_cube_mip_backward")
+        call("gsr_pbr_cube_mip_backward", g.device, n, ch, ptr(g), ptr(out))
         return out
 
 
@@ -89,16 +80,14 @@ class DiffuseFn(torch.autograd.Function):
     def forward(ctx, cube):
         x = _dev(cube, "diffuse_cubemap")
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib.gsr_pbr_diffuse_forward(x.shape[1], ptr(x), ptr(out), _stream(x)), "gsr_pbr_diffuse_forward")
+        call("gsr_pbr_diffuse_forward", x.device, x.shape[1], ptr(x), ptr(out))
         return out
 
     @staticmethod
     def backward(ctx, g):
         g = g.contiguous().float()
         out = torch.empty_like(g)
-        with torch.cuda.device(g.device):
-            check(lib.gsr_pbr_diffuse_backward(g.shape[1], ptr(g), ptr(out), _stream(g)), "gsr_pbr_diffuse_backward")
+        call("gsr_pbr_diffuse_backward", g.device, g.shape[1], ptr(g), ptr(out))
         return out
 
 
@@ -127,9 +116,7 @@ class SpecularFn(torch.autograd.Function):
         out = torch.empty_like(x)
         wsum = torch.empty(6, n, n, device=x.device, dtype=torch.float32)
         cos_cut = ndf_cutoff(roughness, cutoff)
-        with torch.cuda.device(x.device):
-            check(lib.gsr_pbr_specular_forward(n, roughness, cos_cut, ptr(x), ptr(out), ptr(wsum), _stream(x)),
-                  "gsr_pbr_specular_forward")
+        call("gsr_pbr_specular_forward", x.device, n, roughness, cos_cut, ptr(x), ptr(out), ptr(wsum))
         ctx.save_for_backward(wsum)
         ctx.args = (roughness, cos_cut)
         return out
@@ -139,9 +126,7 @@ class SpecularFn(torch.autograd.Function):
         wsum, = ctx.saved_tensors
         g = g.contiguous().float()
         out = torch.empty_like(g)
-        with torch.cuda.device(g.device):
-            check(lib.gsr_pbr_specular_backward(g.shape[1], ctx.args[0], ctx.args[1], ptr(wsum), ptr(g), ptr(out), _stream(g)),
-                  "gsr_pbr_specular_backward")
+        call("gsr_pbr_specular_backward", g.device, g.shape[1], ctx.args[0], ctx.args[1], ptr(wsum), ptr(g), ptr(out))
         return out, None, None
 
 
@@ -158,8 +143,7 @@ class ShadeFn(torch.autograd.Function):
         outs = [torch.empty(n, 3, device=t["normals"].device, dtype=torch.float32) for _ in range(4)]
         s = ShadeFn._struct(t, spec, tone, gamma)
         s.render_rgb, s.diffuse_rgb, s.specular_rgb, s.diffuse_light = (o.data_ptr() for o in outs)
-        with torch.cuda.device(t["normals"].device):
-            check(lib.gsr_pbr_shade_forward(C.byref(s), _stream(t["normals"])), "gsr_pbr_shade_forward")
+        call("gsr_pbr_shade_forward", t["normals"].device, C.byref(s))
         ctx.flags = (tone, gamma)
         ctx.keys = list(t)
         ctx.save_for_backward(*[t[k] for k in t], *spec)
@@ -196,6 +180,5 @@ class ShadeFn(torch.autograd.Function):
         s.diffuse.grad[0] = ptr(d_dif)
         for i, d in enumerate(d_spec):
             s.specular.grad[i] = ptr(d)
-        with torch.cuda.device(t["normals"].device):
-            check(lib.gsr_pbr_shade_backward(C.byref(s), _stream(t["normals"])), "gsr_pbr_shade_backward")
+        call("gsr_pbr_shade_backward", t["normals"].device, C.byref(s))
         return (None, None, None, None, None, None, d_alb, d_rough, d_occ, d_met, d_dif, *d_spec)

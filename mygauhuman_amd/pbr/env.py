@@ -8,14 +8,10 @@ iteration records into graph.GraphedFrame with the light's inputs computed insid
 Tensors must live on the GPU (no CPU path); they are read as contiguous float32."""
 import torch
 
-from .._lib import ENV_TV_AUTO, check, lib, ptr
+from .._lib import ENV_TV_AUTO, call, lib, ptr
 
 # torchvision.transforms.functional.rgb_to_grayscale's weights (the kernel holds the same constants)
 GREY_WEIGHTS = (0.2989, 0.587, 0.114)
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _cube_n(base, what, exc=ValueError):
@@ -48,8 +44,7 @@ def grey_envmap(base, dirs, out=None):
     elif tuple(out.shape) != (1, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != base.device:
         raise ValueError(f"grey_envmap: out must be a contiguous float32 [1, {h}, {w}] tensor on {base.device}")
     b = base.detach().contiguous().float()
-    with torch.cuda.device(base.device):
-        check(lib.gsr_pbr_env_grey(n_face, ptr(b), h * w, ptr(dirs), ptr(out), _stream(b)), "gsr_pbr_env_grey")
+    call("gsr_pbr_env_grey", base.device, n_face, ptr(b), h * w, ptr(dirs), ptr(out))
     return out
 
 
@@ -60,9 +55,7 @@ class _EnvTvFn(torch.autograd.Function):
         h, w = d.shape[-3], d.shape[-2]
         ws = torch.empty(int(lib.gsr_pbr_env_tv_workspace_floats(h, w)), device=b.device, dtype=torch.float32)
         loss = torch.empty((), device=b.device, dtype=torch.float32)
-        with torch.cuda.device(b.device):
-            check(lib.gsr_pbr_env_tv_forward(b.shape[1], ptr(b), h, w, ptr(d), ptr(ws), ptr(loss), _stream(b)),
-                  "gsr_pbr_env_tv_forward")
+        call("gsr_pbr_env_tv_forward", b.device, b.shape[1], ptr(b), h, w, ptr(d), ptr(ws), ptr(loss))
         ctx.save_for_backward(d, ws)
         ctx.args = (b.shape[1], h, w, reduce)
         return loss
@@ -76,9 +69,7 @@ class _EnvTvFn(torch.autograd.Function):
         n_face, h, w, reduce = ctx.args
         d_base = torch.zeros(6, n_face, n_face, 3, device=d.device, dtype=torch.float32)
         up = g.detach().contiguous().float()
-        with torch.cuda.device(d.device):
-            check(lib.gsr_pbr_env_tv_backward(n_face, h, w, ptr(d), ptr(ws), ptr(up), ptr(d_base), reduce, _stream(d)),
-                  "gsr_pbr_env_tv_backward")
+        call("gsr_pbr_env_tv_backward", d.device, n_face, h, w, ptr(d), ptr(ws), ptr(up), ptr(d_base), reduce)
         return d_base, None, None
 
 
@@ -125,6 +116,5 @@ def view_dirs(canonical_rays, world_view_transform, H, W, out=None):
     elif tuple(out.shape) != (H, W, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != m.device:
         raise ValueError(f"view_dirs: out must be a contiguous float32 [{H}, {W}, 3] tensor on {m.device}")
     rays, m = canonical_rays.detach().contiguous().float(), m.detach().contiguous()
-    with torch.cuda.device(m.device):
-        check(lib.gsr_pbr_view_dirs(H * W, ptr(rays), ptr(m), ptr(out), _stream(m)), "gsr_pbr_view_dirs")
+    call("gsr_pbr_view_dirs", m.device, H * W, ptr(rays), ptr(m), ptr(out))
     return out

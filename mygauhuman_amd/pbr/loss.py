@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from .._lib import PbrLoss, check, lib, ptr
+from .._lib import PbrLoss, call, lib, ptr
 
 N_TERMS = 5  # l1, tv, entropy, smooth, prior
 
@@ -28,10 +28,6 @@ def _on_dev(t, what):
 
 def _dev(t, what):
     return _on_dev(t, what).detach().contiguous().float()
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _rgb(t):
@@ -88,8 +84,7 @@ class _PbrLossFn(torch.autograd.Function):
         ws = torch.empty(int(lib.gsr_pbr_loss_workspace_floats()), device=dev, dtype=torch.float32)
         s = spec.struct(rgb, mask, a, b, g0, g1)
         s.loss, s.terms = loss.data_ptr(), terms.data_ptr()
-        with torch.cuda.device(dev):
-            check(lib.gsr_pbr_loss_forward(C.byref(s), ws.data_ptr(), _stream(ws)), "gsr_pbr_loss_forward")
+        call("gsr_pbr_loss_forward", dev, C.byref(s), ws.data_ptr())
         ctx.spec = spec
         ctx.present = [t is not None for t in (rgb, mask, a, b, g0, g1)]
         ctx.save_for_backward(ws, *[t for t in (rgb, mask, a, b, g0, g1) if t is not None])
@@ -111,8 +106,7 @@ class _PbrLossFn(torch.autograd.Function):
         s.d_rgb, s.d_mask, s.d_a, s.d_b = (ptr(o) for o in outs[:4])
         s.d_g[0], s.d_g[1] = ptr(outs[4]), ptr(outs[5])
         if any(o is not None for o in outs):
-            with torch.cuda.device(ws.device):
-                check(lib.gsr_pbr_loss_backward(C.byref(s), ws.data_ptr(), _stream(ws)), "gsr_pbr_loss_backward")
+            call("gsr_pbr_loss_backward", ws.device, C.byref(s), ws.data_ptr())
         return (None, *outs)
 
 

@@ -1,7 +1,7 @@
 """`simple_knn._C.distCUDA2` (SK/spatial.cu:15-26) over the C ABI of libgsr.so."""
 import torch
 
-from .._lib import check, lib
+from .._lib import call, lib
 
 
 def distCUDA2(points):
@@ -16,7 +16,5 @@ def distCUDA2(points):
     if P:
         ws_bytes = lib.gsr_dist2_workspace_bytes(P)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=points.device)
-        with torch.cuda.device(points.device):
-            check(lib.gsr_dist2(P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), ws_bytes,
-                                torch.cuda.current_stream(points.device).cuda_stream), "gsr_dist2")
+        call("gsr_dist2", points.device, P, pts.data_ptr(), means.data_ptr(), ws.data_ptr(), ws_bytes)
     return means
