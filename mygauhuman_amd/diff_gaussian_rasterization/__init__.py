@@ -140,7 +140,7 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, extra, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                sync_free=False, will_backward=True, loss_spec=None):
+                sync_free=False, will_backward=True, loss_spec=None, park_means=None):
         rs = raster_settings
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered,
@@ -162,10 +162,9 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
         num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer, out_extra = out
         ctx.set_materialize_grads(False)  # untouched images arrive as None in backward, not as zero tensors
         # (gradlink) render(): the attribute kernel of this frame consumes the same positions and its backward runs after this one
-        # (it waits for dL_dextra): the position gradient is parked for it to add in-kernel instead of autograd adding the two
-        link = gradlink.current()
-        ctx.park_means = link if (link is not None and link.attr_means_ptr is not None and link.attr_means_ptr == means3D.data_ptr()
-                                  and ctx.needs_input_grad[0] and ctx.needs_input_grad[4]) else None
+        # (it waits for dL_dextra): the position gradient is parked for it to add in-kernel instead of autograd adding the two.
+        # park_means: the frame's link, decided by rasterize_gaussians_multi (it sees the caller's variables), or None
+        ctx.park_means = park_means if (park_means is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[4]) else None
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         # fused phase-1 training loss (_C.Phase1Loss): its value is one more output; the backward forms its image gradients in-kernel
@@ -211,7 +210,7 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
         if ctx.park_means is not None:
             ctx.park_means.means_grad, grad_means3D = grad_means3D, None
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_extra_in, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, None, None, None)
+                grad_rotations, grad_cov3Ds_precomp, None, None, None, None, None)
 
 
 def rasterize_gaussians_multi(means3D, means2D, sh, colors_precomp, extra_colors, opacities, scales, rotations, cov3Ds_precomp,
@@ -236,8 +235,14 @@ def rasterize_gaussians_multi(means3D, means2D, sh, colors_precomp, extra_colors
                                                                   rotations, cov3Ds_precomp))
     if loss_spec is not None and n != 6:
         raise Exception("rasterize_gaussians_multi: the fused phase-1 loss needs all six extra colour sets (normal and axis among them)")
+    # (gradlink) park the position gradient for the attribute kernel's backward only when that backward is certain to run after
+    # this one and to consume it: `means3D` is the variable the attribute call of this frame took and `extra` the feature tensor
+    # it returned (the same objects, not merely the same storage)
+    link = gradlink.current()
+    park = link if (link is not None and will_backward and link.attr_means is not None and link.attr_means() is means3D
+                    and link.attr_features() is extra and means3D.requires_grad and extra.requires_grad) else None
     out = _RasterizeGaussiansMulti.apply(means3D, means2D, sh, colors_precomp, extra, opacities, scales, rotations, cov3Ds_precomp,
-                                         raster_settings, sync_free, will_backward, loss_spec)
+                                         raster_settings, sync_free, will_backward, loss_spec, park)
     if loss_spec is not None:
         return out[0], out[1], out[2], out[3], list(out[4:4 + n]), out[4 + N_EXTRA // 3]
     return out[0], out[1], out[2], out[3], list(out[4:4 + n])

@@ -357,7 +357,7 @@ def test_gradients_joined_in_kernel_equal_autograd_accumulation(oracle, monkeypa
         keys = ("render", "normal", "albedo", "occlusion", "roughness", "world_normal", "render_axis", "render_alpha")
         sum(o[k].mean() * (i + 1) for i, k in enumerate(keys)).backward()
         grads[on] = [None if p.grad is None else p.grad.cpu().numpy() for p in s.model.parameters()]
-    assert len(links) == 1 and links[0].attr_means_ptr is not None and links[0].act_rot_in_ptr is not None   # the linked frame
+    assert len(links) == 1 and links[0].attr_token is not None and links[0].act_rot_in_ptr is not None   # the linked frame
     assert links[0].means_grad is None and links[0].rot_grad is None                                          # nothing left parked
     for ga, gb in zip(grads[False], grads[True]):
         assert (ga is None) == (gb is None)
@@ -366,14 +366,15 @@ def test_gradients_joined_in_kernel_equal_autograd_accumulation(oracle, monkeypa
             util.assert_close("gradient joined in kernel", gb, ga, tol=1e-5, max_bad_frac=0.0)
 
 
-def _chain64(s, leaf, ids, dec=None):
+def _chain64(s, leaf, ids, dec=None, dtype=torch.float64):
     """The reference's per-frame chain from the model's leaf parameters to the rasterizer's inputs, in float64 torch on the CPU
     (scene/gaussian_model.py:157-199 activations, :768-872 LBS with the nearest-vertex ids given, :35-42 covariance,
     gaussian_renderer/__init__.py:128-198 colours and feature colours) -- the differentiable half of the oracle composition.
-    leaf: dict of float64 leaf tensors (requires_grad); dec: optional dict(delta [23,3,3], w [24]) of the motion decoders."""
+    leaf: dict of float64 leaf tensors (requires_grad); dec: optional dict(delta [23,3,3], w [24]) of the motion decoders.
+    dtype: torch.float32 evaluates the same chain in single precision (leaf / dec in that dtype): the checker's own rounding."""
     from tests.test_gpu_lbs import _torch_deform
     from tests.torch_reference import frame_attributes_torch, smpl_pose_transforms_torch
-    t64 = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    t64 = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype)  # noqa: E731
     m = s.m
     smpl = dict(v_template=t64(m["v_template"]), shapedirs=t64(m["shapedirs"]), posedirs=t64(m["posedirs"]),
                 J_regressor=t64(m["J_regressor"]), weights=t64(m["weights"]),
@@ -381,10 +382,10 @@ def _chain64(s, leaf, ids, dec=None):
     V = m["v_template"].shape[0]
     big = dict(poses=t64(BIG_POSE[None]), shapes=t64(np.zeros((1, 10))), R=t64(np.eye(3)), Th=t64(np.zeros((1, 3))))
     tgt = dict(poses=t64(s.pose[None]), shapes=t64(s.betas[None]), R=t64(s.R), Th=t64(s.Th[None]))
-    correct_Rs = None if dec is None else (torch.eye(3, dtype=torch.float64)[None] + dec["delta"])[None]
+    correct_Rs = None if dec is None else (torch.eye(3, dtype=dtype)[None] + dec["delta"])[None]
     A_big, rot_big, _ = smpl_pose_transforms_torch(smpl, big)
     A_pose, rot_pose, _ = smpl_pose_transforms_torch(smpl, tgt, correct_Rs)
-    ident = torch.eye(3, dtype=torch.float64)
+    ident = torch.eye(3, dtype=dtype)
     pd = smpl["posedirs"].reshape(V * 3, -1)
     off_big = (pd @ (rot_big[0, 1:] - ident).reshape(-1)).view(V, 3)
     off_pose = (pd @ (rot_pose[0, 1:] - ident).reshape(-1)).view(V, 3)
@@ -402,7 +403,8 @@ def _chain64(s, leaf, ids, dec=None):
     c = s.cam_np
     cov6, colors, features = frame_attributes_torch(world, transforms, world_normal, scaling, 1.0, leaf["rotation"], rot_n, albedo,
                                                     albedo, opacity.repeat(1, 3), shs, 3, t64(c["campos"]), t64(c["viewmatrix"]))
-    return dict(means3D=world, cov6=cov6, colors=colors, features=features, opacity=opacity, transforms=transforms)
+    return dict(means3D=world, cov6=cov6, colors=colors, features=features, opacity=opacity, transforms=transforms, scaling=scaling,
+                rotation=rot_n)
 
 
 @pytest.mark.parametrize("motion", [False, True], ids=["static_weights", "motion_decoders"])
