@@ -465,7 +465,9 @@ int gsr_knn_nearest(int M, const float *query, int N, const float *ref, int *idx
  *   gsr_sh_grad_from_views: dL_dsh[P][M][3] = scale * sum_v w_k(normalise(means3D - campos_v)) * packed_v, v in fixed
  *     order; `views` holds n_views blocks of view_stride floats: [P*3 packed | campos xyz | padding].  dev_scale (device
  *     pointer to one float, or null) multiplies `scale`: the view-parallel step passes 0 there for a step some rank could not
- *     render (binning overflow), so that every replica skips it, without a host read. */
+ *     render (binning overflow), so that every replica skips it, without a host read.  A view whose three packed values for a
+ *     Gaussian are all zero (culled or invisible there) contributes nothing to that Gaussian, whatever its direction would be:
+ *     a position equal to the view's camera, or a non-finite one, does not reach the sum -- as in the all-reduced path. */
 int gsr_sh_view_pack(int P, const char *geom_buffer, const float *dL_dcolor, float *packed, gsr_stream_t stream);
 int gsr_sh_grad_from_views(int P, int sh_degree, int M, int n_views, const float *means3D, const float *views,
                            size_t view_stride, float scale, const float *dev_scale, float *dL_dsh, gsr_stream_t stream);
@@ -477,7 +479,8 @@ int gsr_sh_grad_from_views(int P, int sh_degree, int M, int n_views, const float
  *     max(SH + 0.5, 0) (a channel that came out 0 was clamped: its gradient is dropped, gaussian_renderer/__init__.py:195),
  *     dL_dcolors = the rasterizer's gradient with respect to them, means3D_view = the view's posed positions, campos device [3].
  *   gsr_sh_grad_from_views_posed: the mean SH gradient written in the model's two parameter layouts, dL_dsh_dc [P][1][3] and
- *     dL_dsh_rest [P][15][3] (16-byte aligned); scale / dev_scale as above. */
+ *     dL_dsh_rest [P][15][3] (16-byte aligned); scale / dev_scale as above, and so is the rule for an all-zero packed triple: the
+ *     view contributes nothing to that Gaussian, whatever position rides in its block. */
 int gsr_sh_view_pack_posed(int P, const float *colors, const float *dL_dcolors, const float *means3D_view, const float *campos,
                            float *view_block, size_t means_offset, size_t cam_offset, gsr_stream_t stream);
 int gsr_sh_grad_from_views_posed(int P, int sh_degree, int n_views, const float *views, size_t view_stride, size_t means_offset,

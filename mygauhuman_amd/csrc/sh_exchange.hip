@@ -57,7 +57,14 @@ __global__ __launch_bounds__(XSH_BLOCK) void sh_grad_from_views_kernel(const ShV
         mx = m[0], my = m[1], mz = m[2];
       }
       const float g0 = blk[3 * (size_t)i], g1 = blk[3 * (size_t)i + 1], g2 = blk[3 * (size_t)i + 2];
-      const float dx = mx - cam[0], dy = my - cam[1], dz = mz - cam[2];
+      const float cx = cam[0], cy = cam[1], cz = cam[2];
+      // A view that packed three zeros for this Gaussian (culled or invisible there, or all channels clamped) contributes
+      // nothing, as in the all-reduced path, which never forms a direction for it (preprocess_bwd.hip: radii <= 0).  Without the
+      // skip a position equal to the view's camera (len = 0) or a non-finite position makes w NaN, and NaN * 0 the whole row.
+      // For finite w no bit changes: acc + w * 0 == acc.  Every load stays above the branch (per lane, in a loop that is uniform
+      // across the wave): the skipped lanes wait out the arithmetic only, no load waits for the comparison.
+      if (g0 == 0.f && g1 == 0.f && g2 == 0.f) continue;
+      const float dx = mx - cx, dy = my - cy, dz = mz - cz;
       const float len = sqrtf(dx * dx + dy * dy + dz * dz);
       float w[16];
 #pragma unroll
