@@ -107,8 +107,9 @@ int gsr_clear_stream_tuning(gsr_stream_t stream);
 
 /* Optional stage timing with HIP events recorded on the caller's stream around the selected stages' kernels
  * (no synchronisation until gsr_profile_read).  Stage ids: 0 forward preprocess, 1 scan, 2 binning (duplicate+sort+
- * ranges or the tile-bucket kernels), 3 blend forward, 4 blend backward, 5 backward preprocess.  stage_mask bit i
- * enables stage i; 0 disables.  gsr_profile_read returns the accumulated milliseconds and launch count of a stage. */
+ * ranges or the tile-bucket kernels), 3 blend forward, 4 blend backward, 5 backward preprocess, 6 blend backward, colours
+ * only (gsr_rasterize_backward_colors, its zero fills included).  stage_mask bit i enables stage i; 0 disables.
+ * gsr_profile_read returns the accumulated milliseconds and launch count of a stage. */
 int gsr_profile_enable(unsigned stage_mask);
 /* Measurement only: while a zero-filled device buffer is registered here, every wave of the blend kernels (default variants)
  * leaves {start, end} in 100 MHz ticks + its list length: forward waves in the first half of the buffer (4 words per wave,
@@ -232,6 +233,26 @@ int gsr_rasterize_backward_ex(int P, int D, int M, int R, const float *backgroun
                               float *dL_dopacity, float *dL_dcolor, float *dL_dmean3D, float *dL_dcov3D, float *dL_dsh,
                               float *dL_dscale, float *dL_drot, int debug, const float *extra_features, int n_extra,
                               const float *const *dL_dout_extra, float *dL_dextra, int sh_dtype, gsr_stream_t stream);
+
+/* The colour columns of the backward alone (extension), for a phase that trains nothing but colours: after pbr_iteration the
+ * reference freezes positions, SH, opacity, scales, rotations and the pose networks (scene/gaussian_model.py:296-306) and its loss
+ * reaches the Gaussians only through the feature images (train.py:294-363), so all a frame needs is
+ *     dL_dcolor[i][c] = sum over pixels of w_i(pixel) dL_dpix[c](pixel),   dL_dextra[i][3 t + c] likewise from dL_dout_extra[t],
+ * with w_i = T_i alpha_i the forward's own blending weight.  The call replays the forward's front-to-back walk (same contributors,
+ * same weights) and forms nothing else: no geometric gradient, no backward preprocess.
+ *   geom / binning / image buffers: as the forward left them (R = its num_rendered, or the capacity of the async forward); they are
+ *     only read -- the gradient accumulation rows inside geom_buffer are not touched, so a gsr_rasterize_backward* call on the same
+ *     buffers before or after it is unaffected, with or without GSR_BWD_ROWS_ZEROED;
+ *   dL_dpix [3][H][W] or null; dL_dcolor [P][3], required when dL_dpix is given (null otherwise allowed);
+ *   n_extra = 0 or 18; dL_dout_extra = HOST array of six device pointers as in gsr_rasterize_backward_ex (a null entry = no
+ *     gradient on that image: no work, its three columns come back exactly zero); dL_dextra [P][18]; both required when n_extra = 18.
+ * Every element of the outputs given is written: the call zero-fills them and accumulates with float atomics (sums agree with
+ * gsr_rasterize_backward_ex to summation order); rows of culled Gaussians stay zero.  "deterministic" = 1 returns GSR_EINVAL, as the
+ * fused 18-channel backward does.  debug bit 0 as elsewhere.  Results do not depend on the binning back-end or on "tile_order" /
+ * "blend_segments" / "tile_cull" (long lists are walked whole, like the forward's). */
+int gsr_rasterize_backward_colors(int P, int R, int width, int height, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                                  const float *dL_dpix, float *dL_dcolor, int n_extra, const float *const *dL_dout_extra,
+                                  float *dL_dextra, int debug, gsr_stream_t stream);
 
 /* The training loss render() feeds before the PBR phase (train.py:261-265 with utils/loss_utils.py:20-24), fused:
  *     L = w_image L1_b(image, gt_image) + w_alpha L2_b(alpha, alpha_target) + w_normal L1_b(normal, gt_normal) + w_axis L1_b(axis, gt_normal)

@@ -41,7 +41,7 @@ def __getattr__(name):
     raise AttributeError(f"module 'mygauhuman_amd' has no attribute {name!r}")
 
 
-def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner=False):
+def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner=False, materials_backward=False):
     """Make `import diff_gaussian_rasterization`, `from simple_knn._C import distCUDA2`, `from knn_cuda import KNN` resolve
     to this package.  render=True also registers `gaussian_renderer` (train.py:17 / render.py import `render` -- and train.py
     `network_gui` -- from it), so that the reference's own drivers reach the fused render() without an edit; the reference's
@@ -52,7 +52,10 @@ def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner
     fused kernels of csrc/pbr.hip.  bake=True registers `baking` (bake_set on the kernels of csrc/bake.hip) and turns on baking
     in render(): at iteration > 30000 a camera without `occlusion` is baked and keeps it.  pose_refiner=True registers
     `nets.mlp_delta_body_pose` (scene/gaussian_model.py imports BodyPoseRefiner from it): the pose-correction network on the fused
-    kernels of csrc/pose_refiner.hip (nets_pose.py), same constructor, same state_dict keys; nets=True alone leaves it alone."""
+    kernels of csrc/pose_refiner.hip (nets_pose.py), same constructor, same state_dict keys; nets=True alone leaves it alone.
+    materials_backward=True sets gaussian_renderer.GEOMETRY_GRAD = "auto": render() takes the materials-only backward
+    (csrc/blend_colors_bwd.hip) whenever none of the model's geometry leaves requires grad -- what update_learning_rate leaves
+    behind after pbr_iteration (scene/gaussian_model.py:296-306).  The default leaves the switch at True: the full backward."""
     pairs = [("diff_gaussian_rasterization", "mygauhuman_amd.diff_gaussian_rasterization"),
              ("simple_knn", "mygauhuman_amd.simple_knn"),
              ("simple_knn._C", "mygauhuman_amd.simple_knn._C"),
@@ -73,3 +76,5 @@ def install_dropin(render=False, nets=False, pbr=False, bake=False, pose_refiner
         sys.modules[theirs] = importlib.import_module(ours)
     if bake:
         importlib.import_module("mygauhuman_amd.gaussian_renderer").BAKE = True
+    if materials_backward:
+        importlib.import_module("mygauhuman_amd.gaussian_renderer").GEOMETRY_GRAD = "auto"

@@ -257,6 +257,8 @@ TABLE["gsr_rasterize_forward_ex"] = _variant("gsr_rasterize_forward", tail=_EX_T
 TABLE["gsr_rasterize_forward_async_ex"] = _variant("gsr_rasterize_forward_async", tail=_EX_TAIL)
 TABLE["gsr_rasterize_backward_ex"] = _variant("gsr_rasterize_backward", tail=[_P, _I, _PP, _P, _I])
 TABLE["gsr_rasterize_backward_phase1_loss"] = _variant("gsr_rasterize_backward_ex", tail=[C.POINTER(Phase1LossStruct)])
+# P, R, width, height, the three buffers, dL_dpix, dL_dcolor, n_extra, dL_dout_extra (host array), dL_dextra, debug
+TABLE["gsr_rasterize_backward_colors"] = (_I, [_I] * 4 + [_P] * 5 + [_I, _PP, _P, _I], STREAM)
 # joint-count (_nj, gsr_body_pose_*) and bone-count (_nb) variants: the same arguments after a leading count
 for _n in ("gsr_lbs_forward", "gsr_lbs_forward_grid", "gsr_lbs_forward_cached", "gsr_lbs_backward"):
     TABLE[_n + "_nj"] = _variant(_n, lead=[_I])
@@ -329,7 +331,7 @@ def ptr(t):
     return t.data_ptr()
 
 
-PROF_STAGES = ["preprocess_fwd", "scan", "binning", "blend_fwd", "blend_bwd", "preprocess_bwd"]
+PROF_STAGES = ["preprocess_fwd", "scan", "binning", "blend_fwd", "blend_bwd", "preprocess_bwd", "blend_bwd_colors"]
 
 
 def profile_enable(stages):

@@ -20,6 +20,7 @@ SOURCES = [
     # buys nothing (v_pk_fma_f32 issues at half the rate of v_fma_f32 on gfx950, profiles/r2_ubench_valu_rate.txt)
     ("blend_fwd.hip", ["-fno-slp-vectorize"]),
     ("blend_bwd.hip", ["-fno-slp-vectorize"]),
+    ("blend_colors_bwd.hip", ["-fno-slp-vectorize"]),
     ("preprocess_bwd.hip", []),
     ("lbs.hip", []),
     ("attributes.hip", []),

@@ -67,8 +67,8 @@ struct ApiState {
   std::atomic<unsigned> prof_mask{0};   // read without the mutex on the fast path (profiling off = two relaxed loads per stage)
   std::vector<ProfRec> prof_recs;                                 // recorded pairs awaiting collection
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;       // recycled events
-  double prof_ms[PROF_NSTAGES] = {0, 0, 0, 0, 0, 0};
-  long prof_n[PROF_NSTAGES] = {0, 0, 0, 0, 0, 0};
+  double prof_ms[PROF_NSTAGES] = {};
+  long prof_n[PROF_NSTAGES] = {};
   // pinned 64-byte slots for the one device->host read of a blocking forward: as many as there are calls in flight at once
   // (one per calling thread at most), recycled -- not one per thread that ever called
   std::mutex pin_mutex;
@@ -857,6 +857,74 @@ int gsr_rasterize_backward_ex(int P, int D, int M, int R, const float *backgroun
                                  geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_ddepths, dL_dalphas, dL_dmean2D, dL_dconic,
                                  dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, extra_features,
                                  n_extra, dL_dout_extra, dL_dextra, sh_dtype, stream);
+}
+
+int gsr_rasterize_backward_colors(int P, int R, int width, int height, char *geom_buffer, char *binning_buffer, char *image_buffer,
+                                  const float *dL_dpix, float *dL_dcolor, int n_extra, const float *const *dL_dout_extra,
+                                  float *dL_dextra, int debug, gsr_stream_t stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (P < 0 || R < 0 || width <= 0 || height <= 0) {
+    set_error("gsr_rasterize_backward_colors: bad sizes");
+    return GSR_EINVAL;
+  }
+  if (n_extra != 0 && n_extra != CE_MAX) {
+    set_error("gsr_rasterize_backward_colors: n_extra must be 0 or %d", CE_MAX);
+    return GSR_EINVAL;
+  }
+  if ((dL_dpix && !dL_dcolor) || (n_extra && (!dL_dout_extra || !dL_dextra))) {
+    set_error("gsr_rasterize_backward_colors: a gradient image needs its output (dL_dpix -> dL_dcolor; n_extra = %d -> dL_dout_extra "
+              "and dL_dextra)", CE_MAX);
+    return GSR_EINVAL;
+  }
+  if (P == 0) return GSR_OK;
+  if (!geom_buffer || !binning_buffer || !image_buffer) {
+    set_error("gsr_rasterize_backward_colors: null required pointer");
+    return GSR_EINVAL;
+  }
+  const Options opt = options_for(stream);
+  if (opt.deterministic) {
+    set_error("gsr_rasterize_backward_colors: no deterministic mode (float atomics only)");
+    return GSR_EINVAL;
+  }
+  const int grid_x = (width + TILE - 1) / TILE, grid_y = (height + TILE - 1) / TILE;
+  const size_t tiles = (size_t)grid_x * grid_y, npix = (size_t)width * height;
+  GeomState geom = geom_from_chunk(geom_buffer, (size_t)P);
+  BinningState bin = binning_from_chunk(binning_buffer, (size_t)R);
+  ImageState img = image_from_chunk(image_buffer, npix, tiles);
+  BlendColorsBwdArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.order = img.order;
+  ca.ranges = img.ranges;
+  ca.point_list = bin.vals_s;
+  ca.recs = geom.recs;
+  ca.W = width;
+  ca.H = height;
+  ca.grid_x = grid_x;
+  ca.grid_y = grid_y;
+  ca.dL_dextra = dL_dextra;
+  ca.dL_dcolor = dL_dcolor;
+  ca.list_prio = opt.blend_prio;
+  for (int t = 0; t <= CE_MAX / 3; t++) {  // the live images, packed: the extra triples, then the main colour
+    const float *g = t < CE_MAX / 3 ? (n_extra ? dL_dout_extra[t] : nullptr) : dL_dpix;
+    if (!g) continue;
+    const int c0 = t < CE_MAX / 3 ? 3 * t : CE_MAX;
+    ca.g_img[ca.n_img] = g;
+    ca.col0 |= (uint64_t)c0 << (5 * ca.n_img);
+    ca.col_mask |= 7u << c0;
+    ca.n_img++;
+  }
+  prof_begin(PROF_BLEND_BWD_COLORS, stream);
+  int rc = GSR_OK;
+  // the outputs are accumulated into: every element the call owns starts at zero (rows of culled Gaussians and the columns of a
+  // null image keep it)
+  if (dL_dcolor && zero_async(dL_dcolor, (size_t)P * 3 * sizeof(float), stream) != hipSuccess) rc = GSR_EHIP;
+  if (rc == GSR_OK && dL_dextra && n_extra && zero_async(dL_dextra, (size_t)P * CE_MAX * sizeof(float), stream) != hipSuccess) rc = GSR_EHIP;
+  if (rc == GSR_OK) rc = launch_blend_colors_backward(ca, stream);
+  prof_end(PROF_BLEND_BWD_COLORS, stream);
+  if (rc == GSR_EHIP) set_error("gsr_rasterize_backward_colors: zero fill failed");
+  if (rc != GSR_OK) return rc;
+  GSR_LAUNCH_CHECK(stream, debug & 1);
+  return GSR_OK;
 }
 
 int gsr_rasterize_backward_phase1_loss(int P, int D, int M, int R, const float *background, int width, int height, const float *means3D,

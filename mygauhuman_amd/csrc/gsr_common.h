@@ -223,7 +223,7 @@ int check_hip(hipError_t e, const char *what, const char *file, int line);
 // ---- optional per-stage HIP-event timing (gsr_api.hip): bench.py brackets the dominant kernel with events on the
 // launch stream inside its timed region.  Disabled (zero cost) unless gsr_profile_enable() selected the stage.
 enum ProfStage { PROF_PREPROCESS_FWD = 0, PROF_SCAN = 1, PROF_BINNING = 2, PROF_BLEND_FWD = 3, PROF_BLEND_BWD = 4,
-                 PROF_PREPROCESS_BWD = 5, PROF_NSTAGES = 6 };
+                 PROF_PREPROCESS_BWD = 5, PROF_BLEND_BWD_COLORS = 6, PROF_NSTAGES = 7 };
 void prof_begin(int stage, hipStream_t stream);
 void prof_end(int stage, hipStream_t stream);
 
@@ -389,6 +389,24 @@ struct BlendBwdArgs {
 int launch_reduce_det_rows(int P, const uint32_t *point_offsets, const uint32_t *tiles_touched, const float *det_rows,
                            size_t n_slots, float *grad_rows, hipStream_t stream);
 int launch_blend_backward(const BlendBwdArgs &a, const Options &opt, hipStream_t stream);
+
+// the colour columns of the blend backward alone (blend_colors_bwd.hip; gsr_rasterize_backward_colors)
+constexpr int CB_IMAGES = CE_MAX / 3 + 1;  // gradient images a call can carry: the six extra triples and the main colour
+struct BlendColorsBwdArgs {
+  const uint32_t *order;  // ImageState::order
+  const uint2 *ranges;
+  const uint32_t *point_list;
+  const SplatRec *recs;
+  int W, H, grid_x, grid_y;
+  const float *g_img[CB_IMAGES];  // the LIVE gradient images [3][H][W], packed to the front
+  int n_img;
+  uint64_t col0;       // 5 bits per live image: its first result column (3 t for extra triple t, CE_MAX for the main colour)
+  uint32_t col_mask;   // bit c: result column c is live
+  float *dL_dextra;    // [P][CE_MAX], zeroed
+  float *dL_dcolor;    // [P][3], zeroed
+  int list_prio;       // Options::blend_prio
+};
+int launch_blend_colors_backward(const BlendColorsBwdArgs &a, hipStream_t stream);
 
 struct PreprocessBwdArgs {
   int P, D, M;

@@ -389,6 +389,52 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
+def rasterize_gaussians_backward_colors(P, R, image_height, image_width, geomBuffer, binningBuffer, imageBuffer, dL_dout_color=None,
+                                        dL_dout_extra=None, debug=False, out=None):
+    """The colour columns of the backward alone (extension; gsr_rasterize_backward_colors): for a frame whose geometry is frozen.
+
+    The three buffers are the forward's (R = its num_rendered, or the capacity of the sync-free forward); they are only read.
+    dL_dout_color: [3,H,W] or None.  dL_dout_extra: None (the frame had no extra colours), a list of six [3,H,W] gradient images
+    (None = that image received no gradient: it costs nothing and its columns come back exactly zero), or one [18,H,W] tensor.
+    `out`: dict with preallocated contiguous float32 tensors "colors" [P,3] / "extra" [P,18].
+    Returns (dL_dcolors [P,3] or None when dL_dout_color is None, dL_dextra [P,18] or None when dL_dout_extra is None)."""
+    dev = geomBuffer.device
+    P, H, W = int(P), int(image_height), int(image_width)
+    opts = dict(dtype=torch.float32, device=dev)
+    out = out or {}
+
+    def _get(name, shape):
+        t = out.get(name)
+        if t is None:
+            return (torch.zeros if P == 0 else torch.empty)(shape, **opts)   # the call writes every element
+        if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"out['{name}'] must be a contiguous float32 tensor of shape {tuple(shape)} on {dev}")
+        return t
+
+    def _image(g, planes, name):
+        if g is None:
+            return None
+        if tuple(g.shape) != (planes, H, W) or g.device != dev:
+            raise RuntimeError(f"{name} must be a [{planes},{H},{W}] tensor on {dev}, got {tuple(g.shape)} on {g.device}")
+        return _f32c(g, name)
+
+    dL_dout_color = _image(dL_dout_color, 3, "dL_dout_color")
+    dL_dcolors = _get("colors", (P, 3)) if dL_dout_color is not None else None
+    dL_dextra, extra_ptrs, n_extra, grads_extra = None, None, 0, ()
+    if dL_dout_extra is not None:
+        if isinstance(dL_dout_extra, torch.Tensor):
+            dL_dout_extra = [_image(dL_dout_extra, _lib.N_EXTRA, "dL_dout_extra")[3 * t:3 * t + 3] for t in range(_lib.N_EXTRA // 3)]
+        if len(dL_dout_extra) != _lib.N_EXTRA // 3:
+            raise RuntimeError(f"dL_dout_extra must hold {_lib.N_EXTRA // 3} gradient images (None for an image without gradient)")
+        grads_extra = [_image(g, 3, "dL_dout_extra") for g in dL_dout_extra]   # kept alive until the launch
+        extra_ptrs = (C.c_void_p * (_lib.N_EXTRA // 3))(*[None if g is None else g.data_ptr() for g in grads_extra])
+        dL_dextra, n_extra = _get("extra", (P, _lib.N_EXTRA)), _lib.N_EXTRA
+    if P != 0:
+        call("gsr_rasterize_backward_colors", dev, P, int(R), W, H, geomBuffer.data_ptr(), binningBuffer.data_ptr(),
+             imageBuffer.data_ptr(), ptr(dL_dout_color), ptr(dL_dcolors), n_extra, extra_ptrs, ptr(dL_dextra), int(bool(debug)))
+    return dL_dcolors, dL_dextra
+
+
 def mark_visible(means3D, viewmatrix, projmatrix):
     """markVisible (DGR/rasterize_points.cu:209-228)."""
     if not means3D.is_cuda:

@@ -140,8 +140,9 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, extra, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                sync_free=False, will_backward=True, loss_spec=None, park_means=None):
+                sync_free=False, will_backward=True, loss_spec=None, park_means=None, geometry_grad=True):
         rs = raster_settings
+        ctx.geometry_grad = bool(geometry_grad)
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
                 rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered,
                 rs.debug)
@@ -164,7 +165,8 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
         # (gradlink) render(): the attribute kernel of this frame consumes the same positions and its backward runs after this one
         # (it waits for dL_dextra): the position gradient is parked for it to add in-kernel instead of autograd adding the two.
         # park_means: the frame's link, decided by rasterize_gaussians_multi (it sees the caller's variables), or None
-        ctx.park_means = park_means if (park_means is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[4]) else None
+        ctx.park_means = park_means if (park_means is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[4]
+                                        and ctx.geometry_grad) else None
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
         # fused phase-1 training loss (_C.Phase1Loss): its value is one more output; the backward forms its image gradients in-kernel
@@ -189,6 +191,16 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer, alpha,
          extra) = ctx.saved_tensors[:12]
         H, W = alpha.shape[-2], alpha.shape[-1]
+        if not ctx.geometry_grad:
+            # frozen geometry: the colour columns alone (gsr_rasterize_backward_colors) -- a replay of the forward's walk; no
+            # geometric sums, no backward preprocess.  Depth and alpha gradients lead only to geometry: ignored.
+            grad_colors_precomp, grad_extra_in = _C.rasterize_gaussians_backward_colors(
+                means3D.shape[0], ctx.num_rendered, H, W, geomBuffer, binningBuffer, imgBuffer,
+                grad_out_color if (ctx.needs_input_grad[3] and colors_precomp.numel()) else None,
+                list(grad_feats) if ctx.needs_input_grad[4] else None, rs.debug)
+            if ctx.watch is not None:
+                _C.AsyncCapacity.check(ctx.watch)
+            return (None, None, None, grad_colors_precomp, grad_extra_in) + (None,) * 10
         phase1 = None
         if grad_loss is not None:   # the fused loss took part in what is being differentiated: images without a further gradient stay None
             phase1 = (ctx.loss_spec, ctx.loss_stats, grad_loss, ctx.saved_tensors[12], ctx.saved_tensors[13])
@@ -210,14 +222,24 @@ class _RasterizeGaussiansMulti(torch.autograd.Function):
         if ctx.park_means is not None:
             ctx.park_means.means_grad, grad_means3D = grad_means3D, None
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_extra_in, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, None, None, None, None)
+                grad_rotations, grad_cov3Ds_precomp, None, None, None, None, None, None)
 
 
 def rasterize_gaussians_multi(means3D, means2D, sh, colors_precomp, extra_colors, opacities, scales, rotations, cov3Ds_precomp,
-                              raster_settings, sync_free=False, loss_spec=None):
+                              raster_settings, sync_free=False, loss_spec=None, geometry_grad=True):
     """Blend the main colour (SHs or colors_precomp) and up to six extra [P,3] colour sets (a list, or one packed [P,18]
     tensor) in one pass.
-    Returns (color, radii, depth, alpha, [image_i [3,H,W] for each extra colour set])."""
+    Returns (color, radii, depth, alpha, [image_i [3,H,W] for each extra colour set]).
+    geometry_grad=False (frozen geometry, the reference's PBR phase): the backward forms the gradients of colors_precomp and of the
+    extra colours only (gsr_rasterize_backward_colors) and returns None for positions, 2D means, opacities, scales, rotations,
+    covariances and SHs; incoming depth and alpha gradients are ignored."""
+    if not geometry_grad:
+        if loss_spec is not None:
+            raise ValueError("rasterize_gaussians_multi: geometry_grad=False cannot carry the fused phase-1 loss (loss_spec): that "
+                             "phase trains the geometry")
+        if isinstance(sh, torch.Tensor) and sh.numel() and sh.requires_grad and torch.is_grad_enabled():
+            raise ValueError("rasterize_gaussians_multi: geometry_grad=False with SHs that require grad: the SH backward is part of "
+                             "the backward preprocess, which this mode does not run (detach them, or pass colors_precomp)")
     P = means3D.shape[0]
     if isinstance(extra_colors, torch.Tensor):  # already packed: [P, 18] = six RGB triples side by side
         if extra_colors.dim() != 2 or extra_colors.shape[1] != N_EXTRA:
@@ -242,7 +264,7 @@ def rasterize_gaussians_multi(means3D, means2D, sh, colors_precomp, extra_colors
     park = link if (link is not None and will_backward and link.attr_means is not None and link.attr_means() is means3D
                     and link.attr_features() is extra and means3D.requires_grad and extra.requires_grad) else None
     out = _RasterizeGaussiansMulti.apply(means3D, means2D, sh, colors_precomp, extra, opacities, scales, rotations, cov3Ds_precomp,
-                                         raster_settings, sync_free, will_backward, loss_spec, park)
+                                         raster_settings, sync_free, will_backward, loss_spec, park, bool(geometry_grad))
     if loss_spec is not None:
         return out[0], out[1], out[2], out[3], list(out[4:4 + n]), out[4 + N_EXTRA // 3]
     return out[0], out[1], out[2], out[3], list(out[4:4 + n])
@@ -276,11 +298,13 @@ class GaussianRasterizer(nn.Module):
                                    self.raster_settings)
 
     def forward_multi(self, means3D, means2D, opacities, extra_colors, shs=None, colors_precomp=None, scales=None, rotations=None,
-                      cov3D_precomp=None, sync_free=False, loss_spec=None):
+                      cov3D_precomp=None, sync_free=False, loss_spec=None, geometry_grad=True):
         """Extension: like forward(), plus `extra_colors` (list of 1..6 [P,3] tensors) blended in the same pass.
         Returns (color, radii, depth, alpha, [extra images]).  sync_free=True skips the host read of num_rendered
         (_C.AsyncCapacity: generous binning capacity, overflow reported at backward / next call).
-        loss_spec (a _C.Phase1Loss): the phase-1 training loss evaluated fused with the pass; its value is appended to the result."""
+        loss_spec (a _C.Phase1Loss): the phase-1 training loss evaluated fused with the pass; its value is appended to the result.
+        geometry_grad=False: the backward returns gradients for colors_precomp and the extra colours only (see
+        rasterize_gaussians_multi); ValueError with loss_spec or with shs that require grad."""
         if (shs is None) == (colors_precomp is None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         has_sr = scales is not None or rotations is not None
@@ -290,4 +314,5 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians_multi(means3D, means2D, empty if shs is None else shs,
                                          empty if colors_precomp is None else colors_precomp, extra_colors, opacities,
                                          empty if scales is None else scales, empty if rotations is None else rotations,
-                                         empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, sync_free, loss_spec)
+                                         empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, sync_free, loss_spec,
+                                         geometry_grad)

@@ -428,8 +428,10 @@ class ViewParallelStep:
         """Block until every issued step has been examined (raises BinningOverflow for an overflowed one)."""
         self.reports.check_all()
 
-    def __call__(self, cam, bg, gt, mask, reduce=True):
+    def __call__(self, cam, bg, gt, mask, reduce=True, geometry_grad=True):
         """Returns (color, alpha, radii); afterwards self.grads[name] holds the (mean over ranks, if reduce) gradients."""
+        if geometry_grad is not True:
+            raise ValueError("ViewParallelStep: geometry_grad must stay True (the materials-only backward has no exchange yet)")
         # by step index, never by event.query(): every rank must raise at the same call
         self.reports.examine(block_older_than=self.reports.issued - self.max_in_flight)
         s, b = self.session, self.bucket
@@ -624,10 +626,16 @@ class ViewParallelRender:
 
     def __call__(self, iteration, camera, loss_fn, reduce=True, **render_kw):
         """loss_fn(out) -> scalar loss of this rank's view.  Returns (out, loss); afterwards p.grad of every leaf holds the mean
-        over the ranks (reduce=True) and the statistics of the step are in .stat_grad_norm / .stat_visible / .max_radii."""
+        over the ranks (reduce=True) and the statistics of the step are in .stat_grad_norm / .stat_visible / .max_radii.
+        render_kw goes to render() with geometry_grad=True always added (whatever gaussian_renderer.GEOMETRY_GRAD says): the
+        exchange is built on the full backward, and geometry_grad=False raises ValueError."""
         from . import attributes
         from .diff_gaussian_rasterization import _C as _RasterC
         from .gaussian_renderer import render
+        # the gradient exchange is built on the full backward (every leaf's bucket slot is filled by it): whatever the module switch
+        # gaussian_renderer.GEOMETRY_GRAD says, the ranks render with it
+        if render_kw.setdefault("geometry_grad", True) is not True:
+            raise ValueError("ViewParallelRender: geometry_grad must stay True (the materials-only backward has no exchange yet)")
         self.reports.examine(block_older_than=self.reports.issued - self.max_in_flight)   # by step index, like ViewParallelStep
         self._rebind_leaves()
         dev, b = self.device, self.bucket
