@@ -369,7 +369,8 @@ int gsr_lbs_forward(int P, int V, const float *query, const float *normals, cons
  * evaluations when the query points lie near the vertex cloud, as canonical Gaussians do.  `workspace` must hold
  * gsr_lbs_workspace_bytes(V) bytes, 16-byte aligned.  grid_is_built != 0: the workspace already holds the grid of exactly
  * these vertices (gsr_lbs_grid_build, or an earlier call) and the rebuild is skipped -- the big-pose vertices of a subject
- * never change between frames. */
+ * never change between frames.  A query point with no finite distance to any vertex (NaN, infinite, or a squared distance
+ * that overflows) takes vertex 0, as in the brute-force scan. */
 size_t gsr_lbs_workspace_bytes(int V);
 int gsr_lbs_grid_build(int V, const float *smpl_verts, char *workspace, size_t workspace_bytes, gsr_stream_t stream);
 int gsr_lbs_forward_grid(int P, int V, const float *query, const float *normals, const float *smpl_verts,
@@ -388,7 +389,10 @@ int gsr_lbs_forward_grid(int P, int V, const float *query, const float *normals,
  * cache_is_valid != 0: one kernel checks every point against its entry and searches (and re-centres) the misses, the
  * skinning takes the ids as given: results bit-identical to the search.  `workspace` must hold the BUILT grid
  * (gsr_lbs_grid_build).  The last 64 bytes of nn_cache are counters: word 1 = searches since the cache was made, word 2 = misses
- * of the last cached call. */
+ * of the last cached call.  A point with no finite distance to any vertex takes vertex 0.  A NaN or infinite point misses and is
+ * searched again every frame; a finite point whose squared distances overflow gets the unbounded radius of a single-vertex cloud
+ * (no other vertex was seen at a finite distance), keeps vertex 0 while its squared displacement stays finite and is searched
+ * again once that overflows: the result equals the search's either way. */
 size_t gsr_lbs_nn_cache_bytes(int P);
 int gsr_lbs_forward_cached(int P, int V, const float *query, const float *normals, const float *smpl_verts,
                            const float *weights, const float *lbs_offsets, const float *A_big, const float *A_pose,
@@ -472,7 +476,8 @@ int gsr_gather_rows(int n_arrays, const float *const *src, float *const *dst, co
  *     knn(xyz, xyz) returns; :176,573,621,671): idx[P][k] int32, dist[P][k].  Workspace: gsr_dist2_workspace_bytes(P).
  *   gsr_knn_nearest: nearest of N reference points for each of M queries (:727, distance of the Gaussians to the SMPL
  *     vertices; :775 is fused into gsr_lbs_forward_grid): idx[M] and/or dist[M] (either may be null).
- *     Workspace: gsr_lbs_workspace_bytes(N), 16-byte aligned. */
+ *     Workspace: gsr_lbs_workspace_bytes(N), 16-byte aligned.  A query with no finite distance to any reference point
+ *     (NaN, infinite, overflowing square) gets index 0 and dist = sqrt(FLT_MAX). */
 int gsr_knn_self(int P, const float *points, int k, int *idx, float *dist, char *workspace, size_t workspace_bytes,
                  gsr_stream_t stream);
 int gsr_knn_nearest(int M, const float *query, int N, const float *ref, int *idx, float *dist, char *workspace,

@@ -50,8 +50,10 @@ __host__ __device__ inline size_t grid_sorted_offset() {
 inline size_t grid_workspace_bytes(int V) { return grid_sorted_offset() + (size_t)V * 16; }
 
 __device__ __forceinline__ int grid_cell_coord(float x, float lo, float inv_h, int dim) {
-  const int c = (int)floorf((x - lo) * inv_h);
-  return min(max(c, 0), dim - 1);
+  // clamped as a float, before the conversion: a NaN or infinite coordinate gets a cell inside the grid (NaN: cell 0) by a
+  // defined path, not by what the conversion instruction happens to return for it
+  const float f = floorf((x - lo) * inv_h);
+  return f > 0.f ? (f < (float)(dim - 1) ? (int)f : dim - 1) : 0;
 }
 
 __global__ __launch_bounds__(GRID_BLOCK) void lbs_grid_build_kernel(int V, const float *verts, char *ws) {
@@ -165,7 +167,10 @@ __device__ __forceinline__ int grid_nearest(const char *ws, const float *q, floa
   const int rmax = max(max(max(c0, d0 - 1 - c0), max(c1, d1 - 1 - c1)), max(c2, d2 - 1 - c2));
   const float eps = 1e-3f * h;  // slack for the rounding of the cell assignment
   float best = FLT_MAX, second = FLT_MAX;
-  int bid = 0x7fffffff;
+  // (a query with no finite distance to any vertex -- NaN, infinite, or so far away that the square overflows -- never
+  // compares below `best`: it keeps vertex 0, the brute-force scan's answer for it.  The first finite candidate always has
+  // d < best, so the tie rule never sees the initial value.)
+  int bid = 0;
   // Rings 0 and 1 in one go: the nine (z, y) rows around q's cell, each ONE contiguous run of the sorted list over x in
   // [c0 - 1, c0 + 1].  All eighteen run bounds are requested before any vertex is looked at: ring by ring (1 + 10 runs, each a
   // pair of dependent loads in front of its vertices) the search was a chain of ~22 memory round trips per point.

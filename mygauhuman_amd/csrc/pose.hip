@@ -27,7 +27,7 @@ struct PoseArgs {
 };
 
 struct Rodrigues {  // intermediates of one joint's axis-angle -> matrix map
-  float angle, d[3], s, c, K[9], KK[9];
+  float angle, d[3], s, c, omc, K[9], KK[9];  // omc = 1 - cos(angle)
 };
 
 __device__ __forceinline__ void mat3_mm(const float *A, const float *B, float *o) {
@@ -56,12 +56,16 @@ __device__ __forceinline__ void rodrigues_fwd(const float *v, Rodrigues &q, floa
   for (int k = 0; k < 3; k++) q.d[k] = v[k] / q.angle;
   q.s = sinf(q.angle);
   q.c = cosf(q.angle);
+  // 1 - cos as 2 sin^2(angle / 2): the difference cancels in float32 (angle = 1e-4: 0 instead of 5e-9), and the backward, which
+  // divides dK by the angle, had four digits fewer in dL/dv there
+  const float sh = sinf(0.5f * q.angle);
+  q.omc = 2.0f * sh * sh;
   const float K[9] = {0.f, -q.d[2], q.d[1], q.d[2], 0.f, -q.d[0], -q.d[1], q.d[0], 0.f};
 #pragma unroll
   for (int k = 0; k < 9; k++) q.K[k] = K[k];
   mat3_mm(q.K, q.K, q.KK);
 #pragma unroll
-  for (int k = 0; k < 9; k++) R[k] = ((k % 4 == 0) ? 1.0f : 0.0f) + q.s * q.K[k] + (1.0f - q.c) * q.KK[k];
+  for (int k = 0; k < 9; k++) R[k] = ((k % 4 == 0) ? 1.0f : 0.0f) + q.s * q.K[k] + q.omc * q.KK[k];
 }
 
 // dL/dv from dL/dR
@@ -77,7 +81,7 @@ __device__ __forceinline__ void rodrigues_bwd(const float *v, const Rodrigues &q
   mat3_mm_nt(dR, q.K, t1);
   mat3_mm_tn(q.K, dR, t2);
 #pragma unroll
-  for (int k = 0; k < 9; k++) dK[k] = q.s * dR[k] + (1.0f - q.c) * (t1[k] + t2[k]);
+  for (int k = 0; k < 9; k++) dK[k] = q.s * dR[k] + q.omc * (t1[k] + t2[k]);
   const float dd[3] = {dK[7] - dK[5], dK[2] - dK[6], dK[3] - dK[1]};
   float da = gs * q.c - gc * q.s;
   da -= (dd[0] * v[0] + dd[1] * v[1] + dd[2] * v[2]) / (q.angle * q.angle);

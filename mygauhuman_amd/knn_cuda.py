@@ -7,8 +7,10 @@ Two exact HIP paths cover every call site of the reference:
   * ref IS query (self k-NN, k <= 3; :176 k = 3, :573/:621/:671 k = 2): Morton-ordered 1024-point boxes with bound pruning
     (csrc/knn.hip, the structure simple-knn uses for distCUDA2), the point itself comes back first at distance 0;
   * k = 1 with any ref (:727 distance to the SMPL vertices, :775 nearest vertex): uniform grid over ref (csrc/lbs.hip).
-Distances are Euclidean, ascending; ties resolve to the lowest index.  KNN_CUDA's own tie-breaking is not documented and the
-package cannot be installed here: parity unpinned, semantics as stated.  No CPU path: CPU tensors raise.
+Distances are Euclidean, ascending; ties resolve to the lowest index.  A k = 1 query with no finite distance to any reference
+point (NaN, infinite, or so far away that the squared distance overflows) gets index 0, never an index outside ref.
+KNN_CUDA's own tie-breaking is not documented and the package cannot be installed here: parity unpinned, semantics as stated.
+No CPU path: CPU tensors raise.
 """
 import torch
 

@@ -1,11 +1,12 @@
 """GPU parity tests of the SMPL LBS kernels: forward against the CPU oracle (oracle/lbs_oracle.c, which is pinned to
-the imported reference smplx.lbs through tests/golden), backward against float64 torch autograd of a restatement of
-the per-point math (the reference relies on autograd for this gradient too).  Tolerance 1e-4 (fp32)."""
+the imported reference smplx.lbs through tests/golden), backward against float64 torch autograd of the restatement of
+the per-point math in tests/deform_reference.py (the reference relies on autograd for this gradient too).  Tolerance 1e-4 (fp32)."""
 import numpy as np
 import pytest
 import torch
 
 from tests import util
+from tests.deform_reference import deform64
 
 pytestmark = pytest.mark.gpu
 
@@ -114,23 +115,6 @@ def test_coarse_deform_c2source_matches_oracle_pipeline(oracle):
     assert len(lbs._CONSTANTS.entries) == n1
 
 
-def _torch_deform(query, normals, loff, A_big, A_pose, off_big, off_shape, off_pose, R, Th, ids, weights):
-    """float64 restatement of the per-point math (gaussian_model.py:776-872) for autograd."""
-    bw = weights[ids]
-    if loff is not None:
-        bw = torch.softmax(torch.log(bw + 1e-9) + loff, dim=-1)
-    Ab = (bw @ A_big.reshape(24, 16)).reshape(-1, 4, 4)
-    Ap = (bw @ A_pose.reshape(24, 16)).reshape(-1, 4, 4)
-    Ri = torch.inverse(Ab[:, :3, :3])
-    q = (Ri @ (query - Ab[:, :3, 3])[..., None])[..., 0]
-    n = (Ri @ normals[..., None])[..., 0]
-    q = q - off_big[ids] + off_shape[ids] + off_pose[ids]
-    src = (Ap[:, :3, :3] @ q[..., None])[..., 0] + Ap[:, :3, 3]
-    sn = (Ap[:, :3, :3] @ n[..., None])[..., 0]
-    Rinv = torch.inverse(R)
-    return src @ Rinv + Th, R @ (Ap[:, :3, :3] @ Ri), sn @ Rinv
-
-
 @pytest.mark.parametrize("with_offsets", [False, True])
 def test_lbs_backward_matches_autograd(oracle, with_offsets):
     from mygauhuman_amd import lbs
@@ -143,8 +127,9 @@ def test_lbs_backward_matches_autograd(oracle, with_offsets):
     t64 = lambda a, g=False: torch.tensor(np.asarray(a, np.float64), requires_grad=g)  # noqa: E731
     rq, rn, rA, ro = t64(c["query"], True), t64(c["normals"], True), t64(c["A_pose"], True), t64(c["off_pose"], True)
     rl = t64(c["loff"], True) if with_offsets else None
-    w, tf, wn = _torch_deform(rq, rn, rl, t64(c["A_big"]), rA, t64(c["off_big"]), t64(c["off_shape"]), ro, t64(c["R"]),
-                              t64(c["Th"]), torch.from_numpy(ids.astype(np.int64)), t64(c["m"]["weights"]))
+    o64 = deform64(rq, rn, rl, t64(c["A_big"]), rA, t64(c["off_big"]), t64(c["off_shape"]), ro, t64(c["R"]),
+                   t64(c["Th"]), torch.from_numpy(ids.astype(np.int64)), t64(c["m"]["weights"]))
+    w, tf, wn = o64["world_pts"], o64["transforms"], o64["world_normals"]
     ((w * t64(gw)).sum() + (tf * t64(gt)).sum() + (wn * t64(gn)).sum()).backward()
     # ---- HIP path
     d = util.to_dev

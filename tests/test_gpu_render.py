@@ -372,7 +372,7 @@ def _chain64(s, leaf, ids, dec=None, dtype=torch.float64):
     gaussian_renderer/__init__.py:128-198 colours and feature colours) -- the differentiable half of the oracle composition.
     leaf: dict of float64 leaf tensors (requires_grad); dec: optional dict(delta [23,3,3], w [24]) of the motion decoders.
     dtype: torch.float32 evaluates the same chain in single precision (leaf / dec in that dtype): the checker's own rounding."""
-    from tests.test_gpu_lbs import _torch_deform
+    from tests.deform_reference import deform64
     from tests.torch_reference import frame_attributes_torch, smpl_pose_transforms_torch
     t64 = lambda a: torch.as_tensor(np.asarray(a, np.float64)).to(dtype)  # noqa: E731
     m = s.m
@@ -396,9 +396,9 @@ def _chain64(s, leaf, ids, dec=None, dtype=torch.float64):
     normal = leaf["normal"] / leaf["normal"].norm(dim=1, keepdim=True)
     P = leaf["xyz"].shape[0]
     loff = None if dec is None else dec["w"][None].expand(P, 24)
-    world, transforms, world_normal = _torch_deform(leaf["xyz"], normal, loff, A_big[0], A_pose[0], off_big, off_shape, off_pose,
-                                                    tgt["R"], tgt["Th"].reshape(3), torch.from_numpy(ids.astype(np.int64)),
-                                                    smpl["weights"])
+    o = deform64(leaf["xyz"], normal, loff, A_big[0], A_pose[0], off_big, off_shape, off_pose, tgt["R"], tgt["Th"].reshape(3),
+                 torch.from_numpy(ids.astype(np.int64)), smpl["weights"])
+    world, transforms, world_normal = o["world_pts"], o["transforms"], o["world_normals"]
     shs = torch.cat((leaf["f_dc"], leaf["f_rest"]), dim=1)
     c = s.cam_np
     cov6, colors, features = frame_attributes_torch(world, transforms, world_normal, scaling, 1.0, leaf["rotation"], rot_n, albedo,

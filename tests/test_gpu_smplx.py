@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import util
+from tests.deform_reference import deform64
 from tests.torch_reference import pose_transforms_torch, rigid_chain, smpl_pose_transforms_torch
 
 pytestmark = pytest.mark.gpu
@@ -51,27 +52,10 @@ def _smpl_dict(b, dev="cuda", dtype=torch.float32):
     return out
 
 
-def _deform64(query, normals, loff, A_big, A_pose, off_big, off_shape, off_pose, R, Th, ids, weights):
-    """float64 restatement of the per-point math (gaussian_model.py:776-872) at any joint count: (world, transforms, normals,
-    translation, bweights)."""
-    J = weights.shape[1]
-    bw = weights[ids]
-    if loff is not None:
-        bw = torch.softmax(torch.log(bw + 1e-9) + loff, dim=-1)
-    Ab = (bw @ A_big.reshape(J, 16)).reshape(-1, 4, 4)
-    Ap = (bw @ A_pose.reshape(J, 16)).reshape(-1, 4, 4)
-    Ri = torch.inverse(Ab[:, :3, :3])
-    d_off = -off_big[ids] + off_shape[ids] + off_pose[ids]
-    q = (Ri @ (query - Ab[:, :3, 3])[..., None])[..., 0] + d_off
-    tr = (Ri @ (-Ab[:, :3, 3])[..., None])[..., 0] + d_off
-    src = (Ap[:, :3, :3] @ q[..., None])[..., 0] + Ap[:, :3, 3]
-    Rinv = torch.inverse(R)
-    world = src @ Rinv + Th
-    transl = ((Ap[:, :3, :3] @ tr[..., None])[..., 0] + Ap[:, :3, 3]) @ Rinv + Th
-    wn = None
-    if normals is not None:
-        wn = ((Ap[:, :3, :3] @ (Ri @ normals[..., None]))[..., 0]) @ Rinv
-    return world, R @ (Ap[:, :3, :3] @ Ri), wn, transl, bw
+def _deform64(*args):
+    """tests/deform_reference.deform64 as the tuple (world, transforms, normals, translation, bweights)."""
+    o = deform64(*args)
+    return o["world_pts"], o["transforms"], o["world_normals"], o["translation"], o["bweights"]
 
 
 def _coarse64(smpl64, query, params, t_params, t_vertices, ids, lbs_weights=None, correct_Rs=None, normals=None):
