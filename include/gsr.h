@@ -451,7 +451,13 @@ int gsr_lbs_backward_nj(int J, int P, int V, const float *query, const float *no
  * padding, C1 = 0.01^2, C2 = 0.03^2 -- over `planes` independent H x W planes (batch x channels of the reference's grouped
  * conv2d).  forward: ssim_map[planes][H][W] (may be null) and the three derivative maps dA, dB, dC (all three or none) that
  * the backward consumes.  backward: dL_dimg1 from dL_dmap[planes][H][W], or from the constant dL_dmap_scalar when dL_dmap is
- * null (the mean reduction of the reference: scalar = upstream / (planes * H * W)).  img2 is the ground truth: no gradient. */
+ * null (the mean reduction of the reference: scalar = upstream / (planes * H * W)).  img2 is the ground truth: no gradient.
+ * dL_dmap weights the map, so it is applied under the window (at the pixel whose map value it scales), not at the output pixel.
+ * The eleven window weights are the reference's float32 values bit for bit: the unnormalised float32 values divided by their sum
+ * rounded ONCE to float32 (what torch's sum returns; a running float32 sum is one ulp lower and scales every weight by 1 + 6e-8).
+ * The same weights serve gsr_ssim_crop_* and the SSIM of gsr_eval_view_finish.  All three round once per operation (built
+ * without FMA contraction), like the reference's elementwise kernels: img1 == img2 gives a map of exactly 1, and the A / B / C
+ * planes of gsr_ssim_crop_forward under the full-frame rectangle are gsr_ssim_forward's bit for bit. */
 int gsr_ssim_forward(int planes, int height, int width, const float *img1, const float *img2, float *ssim_map, float *dA,
                      float *dB, float *dC, gsr_stream_t stream);
 int gsr_ssim_backward(int planes, int height, int width, const float *img1, const float *img2, const float *dL_dmap,

@@ -10,7 +10,11 @@ smallest column and row, w and h the extents, (0, 0, 0, 0) for an empty set), no
 
 The inputs are not stored: tests/ssim_crop_reference.case_inputs() rebuilds them bit for bit from an index hash.  Stored per case
 and group: the rect, the value, and the gradient with respect to img1 INSIDE the rect ([C, h, w]; the slice takes no gradient
-outside it, which the generator asserts)."""
+outside it, which the generator asserts).
+
+Two rendering-like crops follow (tests/image_loss_cases.GOLDEN_CROPS: a flat background and a smooth shaded body, where the
+variances cancel against C2), under their own names with the same three arrays; tests/test_image_loss_reference_host.py holds the
+float64 restatement of tests/image_loss_reference.py to them."""
 import os
 import sys
 import types
@@ -20,6 +24,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
+from tests import image_loss_cases as K  # noqa: E402
 from tests import ssim_crop_reference as R  # noqa: E402
 
 
@@ -46,6 +51,15 @@ def main(ref_root):
             assert not grad.any(), case
             out[f"{case}/{g}/value"] = np.float64(v)
             out[f"{case}/{g}/grad"] = inside.astype(np.float64)
+    import torch
+    for name, (family, H, W, planes, rect) in K.GOLDEN_CROPS.items():
+        a, b = K.make(family, H, W, planes)
+        rx, ry, rw, rh = rect
+        assert rw <= 80 and rh <= 64 and rx >= 0 and ry >= 0 and rx + rw <= W and ry + rh <= H
+        v, grad = R.value_and_grad(torch.from_numpy(a).double(), torch.from_numpy(b).double(), rect, lu.ssim)
+        out[f"{name}/rect"] = np.asarray(rect, np.int32)
+        out[f"{name}/value"] = np.float64(v)
+        out[f"{name}/grad"] = grad[:, ry:ry + rh, rx:rx + rw].astype(np.float64)
     path = os.path.join(HERE, "ssim_crop.npz")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes,", len(out), "arrays")
