@@ -133,6 +133,12 @@ int gsr_mark_visible(int P, const float *means3D, const float *viewmatrix, const
  *   P Gaussians, D active SH degree, M SH coefficients per Gaussian (shs is [P][M][3]);
  *   background[3]; means3D[P][3]; colors_precomp[P][3]; opacities[P]; scales[P][3]; rotations[P][4] (r,x,y,z);
  *   cov3D_precomp[P][6]; viewmatrix/projmatrix[16] (row-vector convention); cam_pos[3];
+ *   scale_modifier: the covariance is built from the float32 product scale_modifier * scales (CR/forward.cu:122-124), and the
+ *   backward's dL_dscale is the gradient with respect to THAT product -- it carries no factor of scale_modifier
+ *   (CR/backward.cu:295,323-325).  So a call with (scale_modifier, scales) equals the call with (1, scale_modifier * scales) in
+ *   every output, dL_dscale included.  D and scale_modifier are by-value kernel arguments: a captured graph keeps them;
+ *   D < the stored degree reads only the first (D + 1)^2 of the M coefficients of a row (the others may hold anything) and
+ *   the backward writes exact zeros into the rest of dL_dsh's row;
  *   out_color[3][H][W], out_depth[H][W], out_alpha[H][W] (alpha = sum of blending weights), radii[P] (may be null).
  * Every element of the outputs is written when P > 0 (the reference binding zero-fills them first,
  * DGR/rasterize_points.cu:69-72; callers only need that for P == 0);

@@ -16,6 +16,8 @@ Rules of a captured region (violations bake a stale pointer or an unqueryable ob
     (R, flags) into a device tensor and leaves its deferred overflow watch out (AsyncCapacity.graph_status keeps those tensors
     for check());
   * the number of Gaussians is baked in: capture again after a densification / pruning step;
+  * the active SH degree (pc.active_sh_degree) and the scale modifier are by-value kernel arguments as well: a captured frame
+    keeps rendering the degree it was recorded at -- capture again after oneupSHdegree();
   * stage profiling (gsr_profile_enable) must be off;
   * ROCm 7.2: under the HIP runtime's graph packet capture (the default) a memset NODE on memory of the graph's pool replays wrong
     as soon as other GPU work runs between two replays (profiles/r3_graph_bisect.txt).  libgsr records none; torch may.  Export

@@ -69,6 +69,13 @@ class HumanGaussianModel:
         m._roughness = t(rng.normal(0, 1, (P, 1)).astype(np.float32))
         return m
 
+    def oneupSHdegree(self):
+        """Activate the next SH band, up to the stored degree (scene/gaussian_model.py:211; train.py:204-206 calls it every 1000
+        iterations).  The degree is a by-value kernel argument: a graph.GraphedFrame captured before the call keeps the old one --
+        capture again."""
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
     # ---- the accessors render() uses (same names as the reference)
     @property
     def get_scaling(self):

@@ -6,7 +6,9 @@ citations file:line): dense over (pixel x Gaussian), torch float64 on the CPU, s
   forward preprocess   CR/forward.cu:155-256 -- near-plane test z <= 0.2 (CR/auxiliary.h:154), projection with
                        p_w = 1 / (w + 1e-7) (CR/forward.cu:199), radius ceil(3 sqrt(lambda_max)) with the 0.1 floor
                        (CR/forward.cu:230-232), tile rect getRect (CR/auxiliary.h:46-56), ndc2pix (CR/auxiliary.h:41-44)
-  3D covariance        CR/forward.cu:118-152 -- the quaternion is used as given, not normalised
+  3D covariance        CR/forward.cu:118-152 -- the quaternion is used as given, not normalised; the scale that enters is
+                       scale_modifier * scale (CR/forward.cu:122-124), and the scale gradient is taken with respect to THAT
+                       product (CR/backward.cu:295,323-325 carry no factor of the modifier): here the modified scale is the leaf
   EWA 2D covariance    CR/forward.cu:74-113 -- t.x / t.z, t.y / t.z clamped to +-1.3 tan(fov/2), J from the clamped t,
                        focal lengths W / (2 tan_fovx), H / (2 tan_fovy) (CR/rasterizer_impl.cu:224-225), +0.3 dilation
   SH -> RGB            CR/forward.cu:20-71 -- direction from campos, +0.5, clamped at 0
@@ -80,7 +82,7 @@ def _near_int(v, rel):
 class _Scene:
     """Per-Gaussian geometry of the visible Gaussians, as a differentiable function of the leaf inputs."""
 
-    def __init__(self, cam, g, bg, mode, grad):
+    def __init__(self, cam, g, bg, mode, grad, scale_modifier=1.0):
         W, H = cam["W"], cam["H"]
         self.W, self.H, self.mode = W, H, mode
         self.gx, self.gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
@@ -89,7 +91,9 @@ class _Scene:
         self.P = P
         self.leaf = {"means3D": _t(g["means3D"]), "opacities": _t(g["opacities"]).reshape(P, 1)}
         if mode == "sh":
-            self.leaf.update(shs=_t(g["shs"]), scales=_t(g["scales"]), rotations=_t(g["rotations"]))
+            # the kernel's float32 modifier times the float32 scales, formed in float64: the leaf of dL_dscales
+            self.leaf.update(shs=_t(g["shs"]), scales=_t(g["scales"]) * float(np.float32(scale_modifier)),
+                             rotations=_t(g["rotations"]))
             self.deg = int(g["sh_degree"])
         else:
             self.leaf.update(cov3D=_t(g["cov3D"]), colors=_t(g["colors"]))
@@ -212,11 +216,12 @@ def _blend(S, geo, p0, p1, want_margin):
     dy = pix[None, :, 1] - _t(py)[:, None]
     power = -0.5 * (con[None, :, 0] * dx * dx + con[None, :, 2] * dy * dy) - con[None, :, 1] * dx * dy
     araw = op[None] * torch.exp(power)
+    one = torch.ones((len(pid), 1), dtype=torch.float64)  # (not ones_like of a column: no Gaussian may be visible at all)
     alpha = araw - (araw - ALPHA_MAX).clamp(min=0).detach()  # min(0.99, o G) with the unclamped gradient
     with torch.no_grad():
         inc = inrect & (power <= 0) & (alpha >= ALPHA_MIN)
         a_inc = torch.where(inc, alpha, torch.zeros_like(alpha))
-        Tb = torch.cumprod(torch.cat([torch.ones_like(a_inc[:, :1]), 1 - a_inc[:, :-1]], 1), 1)
+        Tb = torch.cumprod(torch.cat([one, 1 - a_inc[:, :-1]], 1), 1)
         test = Tb * (1 - a_inc)
         term = inc & (test < T_MIN)
         nterm = torch.cumsum(term.to(torch.int64), 1)
@@ -230,7 +235,7 @@ def _blend(S, geo, p0, p1, want_margin):
             out = dict(margin=m.numpy(), clamped=(keep & (araw > ALPHA_MAX)).any(1).numpy(), terminated=term.any(1).numpy(),
                        n_contrib=keep.sum(1).numpy())
     a_eff = torch.where(keep, alpha, torch.zeros_like(alpha))
-    T = torch.cumprod(torch.cat([torch.ones_like(a_eff[:, :1]), 1 - a_eff], 1), 1)
+    T = torch.cumprod(torch.cat([one, 1 - a_eff], 1), 1)
     wgt = a_eff * T[:, :-1]
     Tf = T[:, -1]
     color = wgt @ geo["rgb"] + Tf[:, None] * S.bg[None]
@@ -244,9 +249,9 @@ def _chunks(S, n_vis):
     return [(p, min(N, p + step)) for p in range(0, N, step)]
 
 
-def forward(cam, g, bg, mode):
+def forward(cam, g, bg, mode, scale_modifier=1.0):
     """Images (float64 numpy, [3,H,W] / [1,H,W] / [1,H,W]), radii, the margin mask [H,W] and coverage statistics."""
-    S = _Scene(cam, g, bg, mode, grad=False)
+    S = _Scene(cam, g, bg, mode, grad=False, scale_modifier=scale_modifier)
     W, H = S.W, S.H
     with torch.no_grad():
         geo = S.per_gaussian()
@@ -268,9 +273,10 @@ def forward(cam, g, bg, mode):
                 z=S.z, flagged=S.flagged)
 
 
-def backward(cam, g, bg, mode, dL_dcolor, dL_ddepth, dL_dalpha):
-    """Gradients of sum(dL_dcolor * color + dL_ddepth * depth + dL_dalpha * alpha), named and shaped as the oracle's."""
-    S = _Scene(cam, g, bg, mode, grad=True)
+def backward(cam, g, bg, mode, dL_dcolor, dL_ddepth, dL_dalpha, scale_modifier=1.0):
+    """Gradients of sum(dL_dcolor * color + dL_ddepth * depth + dL_dalpha * alpha), named and shaped as the oracle's
+    (dL_dscales with respect to scale_modifier * scales, the reference kernel's convention)."""
+    S = _Scene(cam, g, bg, mode, grad=True, scale_modifier=scale_modifier)
     W, H, P = S.W, S.H, S.P
     geo = S.per_gaussian()
     for k in ("ndc", "rgb", "cov6"):

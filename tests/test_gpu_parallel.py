@@ -12,9 +12,15 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("deg,n_views", [(3, 3), (2, 2), (0, 1), (3, 8)])
 def test_compact_sh_exchange_equals_mean_of_view_gradients(deg, n_views):
-    from mygauhuman_amd import _lib, cameras, parallel
     P, W, H = 5000, 160, 112
     cam0, g = util.make_scene(P, W, H, 17, deg)
+    compact_exchange_case(cam0, g, deg, n_views)
+
+
+def compact_exchange_case(cam0, g, deg, n_views):
+    """pack -> gsr_sh_grad_from_views over `n_views` orbit cameras at active degree `deg` (g["shs"] may store more bands)."""
+    from mygauhuman_amd import _lib, cameras, parallel
+    P, W, H = g["means3D"].shape[0], cam0["W"], cam0["H"]
     bg = util.to_dev(np.array([0.1, 0.2, 0.3], np.float32))
     params = dict(means3D=util.to_dev(g["means3D"]), shs=util.to_dev(g["shs"]), opacities=util.to_dev(g["opacities"]),
                   scales=util.to_dev(g["scales"]), rotations=util.to_dev(g["rotations"]))

@@ -40,8 +40,8 @@ def _human_scene(oracle, P=4000, V=1200, W=160, H=128, seed=0, motion=False):
                                  big_verts=big_verts)
 
 
-def _oracle_render(oracle, s, bg):
-    """Compose the oracle pieces: nearest vertex -> LBS -> covariance -> SH colours -> rasterizer."""
+def _oracle_render(oracle, s, bg, deg=3):
+    """Compose the oracle pieces: nearest vertex -> LBS -> covariance -> SH colours (at degree `deg`) -> rasterizer."""
     m, g = s.m, s.g
     rot_big, rot_pose = oracle.rodrigues(BIG_POSE), oracle.rodrigues(s.pose)
     A_big, _ = oracle.joint_transforms(m, np.zeros(10, np.float32), rot_big)
@@ -62,7 +62,7 @@ def _oracle_render(oracle, s, bg):
     from mygauhuman_amd.sh_utils import eval_sh
     dirs = o["world_src"] - s.cam_np["campos"]
     dirs = dirs / np.linalg.norm(dirs, axis=1, keepdims=True)
-    rgb = eval_sh(3, torch.from_numpy(np.ascontiguousarray(g["shs"].transpose(0, 2, 1))), torch.from_numpy(dirs)).numpy()
+    rgb = eval_sh(deg, torch.from_numpy(np.ascontiguousarray(g["shs"].transpose(0, 2, 1))), torch.from_numpy(dirs)).numpy()
     colors = np.maximum(rgb + 0.5, 0).astype(np.float32)
     c = s.cam_np
     return oracle.rasterize_forward(o["world_src"], g["opacities"], c["viewmatrix"], c["projmatrix"], c["campos"], c["W"], c["H"],

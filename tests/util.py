@@ -17,8 +17,21 @@ def make_scene(P, W, H, seed=0, deg=3, scale=0.02, behind_frac=0.0):
     return cam, g
 
 
-def oracle_forward(oracle, cam, g, bg, mode):
-    kw = dict(scale_modifier=1.0)
+def stored_above_active(g, D, inactive_gain=50.0):
+    """A copy of scene `g` (made at its STORED degree) whose active degree is D < stored: g["sh_degree"] = D and the coefficients of
+    the bands above D times `inactive_gain` -- a kernel that reads one band too many, or strides by (D + 1)^2 rows instead of M, is
+    then wrong by far more than any tolerance.  The oracle (degree= apart from shs.shape[1]) and tests/raster_reference.py
+    (g["sh_degree"]) take the two numbers apart."""
+    out = dict(g)
+    out["sh_degree"] = int(D)
+    out["shs"] = g["shs"].copy()
+    assert (D + 1) ** 2 <= out["shs"].shape[1]
+    out["shs"][:, (D + 1) ** 2:] *= np.float32(inactive_gain)
+    return out
+
+
+def oracle_forward(oracle, cam, g, bg, mode, scale_modifier=1.0):
+    kw = dict(scale_modifier=float(scale_modifier))
     if mode == "sh":
         kw.update(scales=g["scales"], rotations=g["rotations"], shs=g["shs"], degree=g["sh_degree"])
     else:
@@ -31,18 +44,21 @@ def to_dev(a, dev="cuda"):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
-def hip_forward(cam, g, bg, mode, debug=False, dev="cuda"):
-    """Forward through the raw binding (same 19 positional args as the reference's _C.rasterize_gaussians)."""
+def hip_forward(cam, g, bg, mode, debug=False, dev="cuda", scale_modifier=1.0, shs=None):
+    """Forward through the raw binding (same 19 positional args as the reference's _C.rasterize_gaussians).
+    shs: a device tensor handed to the binding as it is instead of g["shs"] (another dtype, another alignment)."""
     from mygauhuman_amd.diff_gaussian_rasterization import _C
     e = torch.empty(0)
-    t = {k: to_dev(v, dev) for k, v in g.items() if isinstance(v, np.ndarray)}
+    t = {k: to_dev(v, dev) for k, v in g.items() if isinstance(v, np.ndarray) and not (k == "shs" and shs is not None)}
+    if shs is not None:
+        t["shs"] = shs
     args = dict(bg=to_dev(bg, dev), means3D=t["means3D"], opac=t["opacities"], view=to_dev(cam["viewmatrix"], dev),
                 proj=to_dev(cam["projmatrix"], dev), campos=to_dev(cam["campos"], dev))
     if mode == "sh":
         colors, scales, rots, cov, sh, deg = e, t["scales"], t["rotations"], e, t["shs"], g["sh_degree"]
     else:
         colors, scales, rots, cov, sh, deg = t["colors"], e, e, t["cov3D"], e, 0
-    out = _C.rasterize_gaussians(args["bg"], args["means3D"], colors, args["opac"], scales, rots, 1.0, cov, args["view"],
+    out = _C.rasterize_gaussians(args["bg"], args["means3D"], colors, args["opac"], scales, rots, float(scale_modifier), cov, args["view"],
                                  args["proj"], cam["tanfovx"], cam["tanfovy"], cam["H"], cam["W"], sh, deg,
                                  args["campos"], False, debug)
     R, color, depth, alpha, radii, geomB, binB, imgB = out
@@ -56,12 +72,12 @@ def hip_query(f, what):
     return _C.query_state(what, f["P"], f["R"], f["W"], f["H"], f["geom"], f["bin"], f["img"]).cpu().numpy()
 
 
-def hip_backward(f, dL_dcolor, dL_ddepth, dL_dalpha, debug=False):
+def hip_backward(f, dL_dcolor, dL_ddepth, dL_dalpha, debug=False, scale_modifier=1.0):
     from mygauhuman_amd.diff_gaussian_rasterization import _C
     a, cam = f["args"], f["cam"]
     dev = a["means3D"].device
     out = _C.rasterize_gaussians_backward(
-        a["bg"], a["means3D"], f["radii"], f["colors"], f["scales"], f["rots"], 1.0, f["cov"], a["view"], a["proj"],
+        a["bg"], a["means3D"], f["radii"], f["colors"], f["scales"], f["rots"], float(scale_modifier), f["cov"], a["view"], a["proj"],
         cam["tanfovx"], cam["tanfovy"], to_dev(dL_dcolor, dev), to_dev(dL_ddepth, dev), to_dev(dL_dalpha, dev), f["sh"],
         f["deg"], a["campos"], f["geom"], f["R"], f["bin"], f["img"], f["alpha"], debug)
     names = ["dL_dmean2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations"]
