@@ -806,7 +806,11 @@ int gsr_pbr_view_dirs(int n, const float *rays, const float *world_view_transfor
  * them, instances[1] = the largest cell's (blocks).  gsr_bake_visibility writes vis[C][ndir] = 1 - the rasterizer's alpha (sum of
  * alpha T) at each direction's texel of cell c's cube, rendered without cell c's Gaussians; it processes cells in batches that fit
  * the workspace (20 bytes per instance beside gsr_bake_visibility_workspace_bytes(C, 0); tuning key "bake_batch_cells" caps a
- * batch) and fills stats[4] (may be null): instances, largest batch, batches, capacity. */
+ * batch) and fills stats[4] (may be null): instances, largest batch, batches, capacity.
+ * Rule: a direction whose dir_texel is outside [0, 6144) (baking.cube_nearest_texel gives -1 for a zero or non-finite direction)
+ * needs no texel and gets NaN in vis, in every row; the other columns do not depend on it.  bake_set never produces such a
+ * direction (its 16 x 32 equirect directions all have a texel); the fused=False composition (baking.cube_nearest) reads alpha 0
+ * there, which gives 1.0. */
 typedef struct gsr_bake_scene {
   int P, C;                                            /* Gaussians, occupied cells */
   const float *means3D, *scales, *rotations, *opacities; /* [P][3] posed means, [P][3] / [P][4] canonical scales / rotations, [P] */
