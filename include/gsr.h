@@ -481,6 +481,56 @@ int gsr_ssim_backward(int planes, int height, int width, const float *img1, cons
 int gsr_gather_rows(int n_arrays, const float *const *src, float *const *dst, const int *row_floats, const int *zero_new,
                     int n_out, const int *index, gsr_stream_t stream);
 
+/* The decisions and the new rows of a densification step on the device (extension; csrc/densify.hip): what surrounds
+ * gsr_gather_rows in densify_and_clone / densify_and_split / kl_densify_and_clone / kl_densify_and_split / kl_merge /
+ * prune_points (scene/gaussian_model.py:443-461,514-708,740-762) without a host read.  All arrays are device arrays unless
+ * stated otherwise; none may alias an output.
+ *
+ *   gsr_kl_pairs: kl[i] = KL( N(mu_a, S_a) || N(mu_b, S_b) ), (a, b) = pairs[i], S = R diag(s^2) R^T with R of the normalised
+ *     quaternion rotation[.] (w, x, y, z) and s = exp(log_scaling[.]) -- kl_div (:740-762) evaluated in the frame of b, where
+ *     every summand of the trace and of the Mahalanobis term is non-negative and the log-determinant is 2 sum(l_b - l_a).
+ *     A pair index outside [0, P) gives NaN and reads nothing.
+ *   gsr_densify_select: flags[i] = 1 where Gaussian i is selected, else 0.  `scaling` is the ACTIVATED scaling [P][3], grads
+ *     [n_grads] (n_grads <= P; rows beyond it count as 0):
+ *       GSR_DENSIFY_CLONE  |grads[i]| >= grad_threshold and max(scaling[i]) <= size_threshold   [and kl[i] > kl_threshold]
+ *       GSR_DENSIFY_SPLIT   grads[i]  >= grad_threshold and max(scaling[i]) >  size_threshold   [and kl[i] > kl_threshold]
+ *       GSR_DENSIFY_MERGE   grads[i]  >= grad_threshold and max(scaling[i]) <= size_threshold   [and kl[i] < kl_threshold]
+ *     (the KL term only with kl != null).  A NaN on either side of a comparison makes it false.
+ *   gsr_densify_plan: the row plan (the `index` of gsr_gather_rows, bit 30 = new row) of an operation from its flags, by a
+ *     stable compaction; header = (n_keep, n_new, n_out, 0), n_out = n_keep + n_new plan entries are written:
+ *       GSR_PLAN_PRUNE  the rows with flag 0, in order                                              plan capacity P
+ *       GSR_PLAN_CLONE  all P rows, then the flagged rows (new)                                                   2 P
+ *       GSR_PLAN_SPLIT  the rows with flag 0, then N times the flagged rows in order (new)                  (N + 1) P
+ *       GSR_PLAN_MERGE  the rows that are neither flagged nor pairs[i][1] of a flagged i, then pairs[i][0]        2 P
+ *                       (new) for every flagged i in order; plan[P + c] = pairs[i][1] of the c-th of them (n_out <= P)
+ *     The same input gives the same plan on every call (positions come from prefix sums).  (N + 1) P < 2^30.  Workspace:
+ *     gsr_densify_plan_workspace_bytes(P), 4-byte aligned.
+ *   gsr_build_rows: gsr_gather_rows (same host tables; n_src = rows of the source arrays, an index beyond it gives NaN)
+ *     that also computes the new rows, i.e. the output rows j >= first, of the arrays whose role[] (host array) is not
+ *     GSR_ROW_COPY; s = index[j] & 0x3FFFFFFF, c = j - first, `scaling` = the activated scaling [n_src][3]:
+ *       GSR_BUILD_MOVE      nothing is computed (role, first, scaling, unit, partner are ignored)
+ *       GSR_BUILD_CHILDREN  GSR_ROW_XYZ: R(rotation[s]) (scaling[s] * unit[c]) + xyz[s];  GSR_ROW_LOG_SCALING: log(scaling[s]
+ *                           / divisor).  xyz / rotation are the source arrays with role GSR_ROW_XYZ / GSR_ROW_ROTATION and
+ *                           zero_new = 0 (the parameters, not their moments); unit [n_out - first][3].
+ *       GSR_BUILD_MERGE     GSR_ROW_XYZ and GSR_ROW_MEAN: 0.5 (src[s] + src[partner[c]]);  GSR_ROW_LOG_SCALING: log(scaling[s]
+ *                           / 0.8); partner [n_out - first] (a row outside [0, n_src) gives NaN).
+ *     Rows below `first`, arrays with role GSR_ROW_COPY / GSR_ROW_ROTATION and zeroed rows are as in gsr_gather_rows. */
+enum { GSR_DENSIFY_CLONE = 0, GSR_DENSIFY_SPLIT = 1, GSR_DENSIFY_MERGE = 2 };
+enum { GSR_PLAN_PRUNE = 0, GSR_PLAN_CLONE = 1, GSR_PLAN_SPLIT = 2, GSR_PLAN_MERGE = 3 };
+enum { GSR_BUILD_MOVE = 0, GSR_BUILD_CHILDREN = 1, GSR_BUILD_MERGE = 2 };
+enum { GSR_ROW_COPY = 0, GSR_ROW_XYZ = 1, GSR_ROW_LOG_SCALING = 2, GSR_ROW_ROTATION = 3, GSR_ROW_MEAN = 4 };
+int gsr_kl_pairs(int P, const float *xyz, const float *rotation, const float *log_scaling, const int *pairs, float *kl,
+                 gsr_stream_t stream);
+int gsr_densify_select(int P, int mode, const float *grads, int n_grads, const float *scaling, const float *kl,
+                       float grad_threshold, float size_threshold, float kl_threshold, unsigned char *flags,
+                       gsr_stream_t stream);
+size_t gsr_densify_plan_workspace_bytes(int P);
+int gsr_densify_plan(int P, int kind, int N, const unsigned char *flags, const int *pairs, int *plan, int *header,
+                     char *workspace, size_t workspace_bytes, gsr_stream_t stream);
+int gsr_build_rows(int n_arrays, const float *const *src, float *const *dst, const int *row_floats, const int *zero_new,
+                   const int *role, int n_out, const int *index, int n_src, int first, int mode, const float *scaling,
+                   const float *unit, float divisor, const int *partner, gsr_stream_t stream);
+
 /* k-NN service replacing the un-vendored KNN_CUDA dependency (scene/gaussian_model.py:87-89).
  * Semantics assumed for KNN_CUDA 0.2 (parity unpinned): exact brute-force k-NN, Euclidean distances in ascending order;
  * here ties resolve to the lowest index.

@@ -162,6 +162,12 @@ TABLE = {
     "gsr_knn_self": (_I, [_I, _P, _I, _P, _P, _P, _Z], STREAM),
     "gsr_knn_nearest": (_I, [_I, _P, _I, _P, _P, _P, _P, _Z], STREAM),
     "gsr_gather_rows": (_I, [_I, _PP, _PP, _IP, _IP, _I, _P], STREAM),
+    # densification: pair KL, selections, row plans, rows with the new ones computed
+    "gsr_kl_pairs": (_I, [_I] + [_P] * 5, STREAM),
+    "gsr_densify_select": (_I, [_I, _I, _P, _I, _P, _P, _F, _F, _F, _P], STREAM),
+    "gsr_densify_plan_workspace_bytes": (_Z, [_I], PLAIN),
+    "gsr_densify_plan": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _Z], STREAM),
+    "gsr_build_rows": (_I, [_I, _PP, _PP, _IP, _IP, _IP, _I, _P, _I, _I, _I, _P, _P, _F, _P], STREAM),
     # skinning, pose chain, pose blend shapes
     "gsr_lbs_workspace_bytes": (_Z, [_I], PLAIN),
     "gsr_lbs_grid_build": (_I, [_I, _P, _P, _Z], STREAM),
@@ -281,6 +287,10 @@ DEFAULT_TILE_CULL = 1  # tuning knob "tile_cull": exact ellipse-vs-tile culling 
 DEFAULT_BWD_REDUCE = 3
 DEFAULT_TILE_ORDER = 1  # tuning knob "tile_order" (csrc/gsr_common.h: Options)
 DEFAULT_BLEND_LAYOUT = 0  # tuning knob "blend_layout"
+DENSIFY_CLONE, DENSIFY_SPLIT, DENSIFY_MERGE = 0, 1, 2  # mode of gsr_densify_select
+PLAN_PRUNE, PLAN_CLONE, PLAN_SPLIT, PLAN_MERGE = 0, 1, 2, 3  # kind of gsr_densify_plan
+BUILD_MOVE, BUILD_CHILDREN, BUILD_MERGE = 0, 1, 2  # mode of gsr_build_rows
+ROW_COPY, ROW_XYZ, ROW_LOG_SCALING, ROW_ROTATION, ROW_MEAN = 0, 1, 2, 3, 4  # role of an array in gsr_build_rows
 ENV_TV_AUTO, ENV_TV_WINDOW, ENV_TV_WHOLE = 0, 1, 2  # gsr_pbr_env_tv_backward's reduce (include/gsr.h)
 DEFAULT_BLEND_SEGMENTS = 8  # tuning knob "blend_segments": lists >= 8 / 4 x the frame's mean are walked in segments
 

@@ -28,6 +28,8 @@ SOURCES = [
     ("pose.hip", []),
     ("sh_exchange.hip", []),
     ("rows.hip", []),
+    # one rounding per operation, like the torch expressions the new rows and the pair divergences are held against
+    ("densify.hip", ["-ffp-contract=off"]),
     # the SSIM tile bodies (these two and eval.hip's) round once per operation, like the reference's elementwise kernels: identical
     # planes then give a map of exactly 1, and the three copies agree (tests/test_gpu_image_loss_f64.py)
     ("ssim.hip", ["-ffp-contract=off"]),

@@ -12,6 +12,15 @@ indexing and torch.cat -- about 90 kernels and 30 host synchronisations per oper
 30 arrays by ONE HIP kernel (gsr_gather_rows, csrc/rows.hip); the nearest-SMPL-vertex distance of the prune test comes from
 the grid k-NN (gsr_knn_nearest).  The plan builders are plain tensor code (also runs on CPU, tests/test_densify_cpu.py);
 applying a plan needs the GPU library.
+
+fused=True (opt-in, every operation; csrc/densify.hip) takes the rest to the device as well: the pair divergences of the KL
+variants come from ONE kernel on the raw parameters (gsr_kl_pairs, no gathers, no [P,3,3] temporaries), the selection is one
+kernel (gsr_densify_select), the row plan a device-side stable compaction that leaves its counts in a 4-int header
+(gsr_densify_plan, through device_plan(): no torch.nonzero, no host read), and the rows are built by gsr_build_rows, which is
+gsr_gather_rows plus the arithmetic of the new rows (split children, displaced KL clones, merged means), so that no torch op
+touches the result afterwards.  An operation is then select -> plan -> ONE host read (the header, in apply_device_plan: the
+output sizes) -> build rows.  Selections, plans and moved rows are bit-identical to the default path; recomputed rows agree to
+float32 rounding.
 """
 import ctypes as C
 
@@ -19,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import covariance
+from . import _lib
 from ._lib import call
 
 GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "normal", "albedo", "roughness")
@@ -77,15 +87,13 @@ def _arrays(model):
     return out
 
 
-def apply_plan(model, plan, reset_stats):
-    """Move every per-Gaussian array of `model` (parameters, Adam moments, statistics) to the row set `plan` describes and
-    re-register the parameters with the optimizer the way _prune_optimizer / cat_tensors_to_optimizer do."""
+def _row_tables(model, n_out, reset_stats):
+    """What a row kernel needs for every per-Gaussian array of `model`: (arrays, sources, freshly allocated outputs [n_out, ...],
+    row widths, zero_new flags, the indices of the arrays that are moved).  With reset_stats the statistics are zero-filled
+    here and not moved (densification_postfix restarts them for the whole new set)."""
     dev = model._xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("densify: applying a row plan needs the HIP library (tensors must live on the GPU)")
     arrays = _arrays(model)
-    n_out = int(plan.shape[0])
-    srcs, dsts, widths, zero_new, outs = [], [], [], [], []
+    srcs, widths, zero_new, outs = [], [], [], []
     for kind, name, t, zn in arrays:
         t2 = t.detach().contiguous().float()
         w = 1
@@ -102,15 +110,11 @@ def apply_plan(model, plan, reset_stats):
                 outs[i].zero_()
     # zero-width arrays (f_rest at SH degree 0) have nothing to move
     move = [i for i, (kind, _, _, _) in enumerate(arrays) if not (kind == "stat" and reset_stats) and widths[i] > 0]
-    if n_out and move:
-        n = len(move)
-        plan_c = plan.to(device=dev, dtype=torch.int32).contiguous()
-        src_p = (C.c_void_p * n)(*[srcs[i].data_ptr() for i in move])
-        dst_p = (C.c_void_p * n)(*[outs[i].data_ptr() for i in move])
-        w_p = (C.c_int * n)(*[widths[i] for i in move])
-        z_p = (C.c_int * n)(*[zero_new[i] for i in move])
-        call("gsr_gather_rows", dev, n, src_p, dst_p, w_p, z_p, n_out, plan_c.data_ptr())
-    # re-register (scene/gaussian_model.py:421-441,463-486)
+    return arrays, srcs, outs, widths, zero_new, move
+
+
+def _reregister(model, arrays, outs):
+    """Make `outs` the model's parameters, Adam moments and statistics (scene/gaussian_model.py:421-441,463-486)."""
     by = {(kind, name): o for (kind, name, _, _), o in zip(arrays, outs)}
     for g in GROUPS:
         old = getattr(model, ATTR[g])
@@ -128,6 +132,134 @@ def apply_plan(model, plan, reset_stats):
     model.xyz_gradient_accum = by[("stat", "xyz_gradient_accum")]
     model.denom = by[("stat", "denom")]
     model.max_radii2D = by[("stat", "max_radii2D")]
+
+
+def apply_plan(model, plan, reset_stats):
+    """Move every per-Gaussian array of `model` (parameters, Adam moments, statistics) to the row set `plan` describes and
+    re-register the parameters with the optimizer the way _prune_optimizer / cat_tensors_to_optimizer do."""
+    dev = model._xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("densify: applying a row plan needs the HIP library (tensors must live on the GPU)")
+    n_out = int(plan.shape[0])
+    arrays, srcs, outs, widths, zero_new, move = _row_tables(model, n_out, reset_stats)
+    if n_out and move:
+        n = len(move)
+        plan_c = plan.to(device=dev, dtype=torch.int32).contiguous()
+        src_p = (C.c_void_p * n)(*[srcs[i].data_ptr() for i in move])
+        dst_p = (C.c_void_p * n)(*[outs[i].data_ptr() for i in move])
+        w_p = (C.c_int * n)(*[widths[i] for i in move])
+        z_p = (C.c_int * n)(*[zero_new[i] for i in move])
+        call("gsr_gather_rows", dev, n, src_p, dst_p, w_p, z_p, n_out, plan_c.data_ptr())
+    _reregister(model, arrays, outs)
+
+
+# ---------------------------------------------------------------- the same on the device (fused=True; csrc/densify.hip)
+PLAN_KINDS = dict(prune=_lib.PLAN_PRUNE, clone=_lib.PLAN_CLONE, split=_lib.PLAN_SPLIT, merge=_lib.PLAN_MERGE)
+SELECT_MODES = dict(clone=_lib.DENSIFY_CLONE, split=_lib.DENSIFY_SPLIT, merge=_lib.DENSIFY_MERGE)
+# the arrays a merge averages over the pair; the roles of the parameters gsr_build_rows computes new rows from or for
+MERGE_MEAN = ("xyz", "f_dc", "f_rest", "opacity", "normal", "albedo", "roughness")
+_ROLES = dict(xyz=_lib.ROW_XYZ, scaling=_lib.ROW_LOG_SCALING, rotation=_lib.ROW_ROTATION)
+
+
+def _need_hip(what, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{what}: tensors must live on a HIP device (no CPU path)")
+
+
+def device_select(mode, grads, scaling, grad_threshold, size_threshold, kl=None, kl_threshold=0.0):
+    """flags [P] uint8 of clone_mask / split_mask / the merge selection, `and` the KL test when `kl` is given ("clone", "split":
+    kl > kl_threshold; "merge": kl < kl_threshold).  grads: [n, 1] or [n] with n <= P ("clone": the norm over the last axis when
+    it is wider); scaling: the ACTIVATED scaling [P, 3].  One launch, no host synchronisation."""
+    _need_hip("device_select", grads, scaling, kl)
+    P, dev = scaling.shape[0], scaling.device
+    flags = torch.empty((P,), dtype=torch.uint8, device=dev)
+    if P == 0:
+        return flags
+    if grads.dim() > 1 and grads.shape[-1] != 1:
+        if mode != "clone":
+            raise ValueError("device_select: split and merge take one gradient value per Gaussian")
+        grads = torch.norm(grads, dim=-1)
+    g = grads.detach().reshape(-1).contiguous().float()
+    sc = scaling.detach().contiguous().float()
+    klc = None if kl is None else kl.detach().contiguous().float()
+    call("gsr_densify_select", dev, P, SELECT_MODES[mode], _lib.ptr(g), g.shape[0], sc.data_ptr(), _lib.ptr(klc),
+         float(grad_threshold), float(size_threshold), float(kl_threshold), flags.data_ptr())
+    return flags
+
+
+def plan_capacity(kind, P, N=2):
+    return {"prune": P, "clone": 2 * P, "split": (N + 1) * P, "merge": 2 * P}[kind]
+
+
+def device_plan(kind, flags, N=2, pairs=None):
+    """(plan, header) of plan_prune / plan_clone / plan_split / the merge plan of kl_merge, built on the device from `flags`
+    [P] (uint8 or bool; non-zero = selected; for "prune": the rows to remove) without a host synchronisation.
+    plan: int32 [plan_capacity(kind, P, N)], its first header[2] entries are the plan; header: int32 [4] on the device =
+    (rows kept, new rows, rows in all, 0).  "merge" needs pairs [P, 2] (int32 / int64: every Gaussian and its partner) and
+    leaves the partners of the merged rows at plan[P : P + header[1]]."""
+    _need_hip("device_plan", flags, pairs)
+    if kind not in PLAN_KINDS:
+        raise ValueError(f"device_plan: kind is one of {sorted(PLAN_KINDS)}")
+    P, dev = flags.shape[0], flags.device
+    header = torch.zeros((4,), dtype=torch.int32, device=dev)
+    plan = torch.empty((plan_capacity(kind, P, N),), dtype=torch.int32, device=dev)
+    if P == 0:
+        return plan, header
+    f = flags.detach().contiguous()
+    f = f.view(torch.uint8) if f.dtype == torch.bool else f.to(torch.uint8)
+    pr = None
+    if kind == "merge":
+        if pairs is None:
+            raise ValueError("device_plan: a merge plan needs the pairs")
+        pr = pairs.detach().to(torch.int32).contiguous()
+    ws = torch.empty((_lib.lib.gsr_densify_plan_workspace_bytes(P),), dtype=torch.uint8, device=dev)
+    call("gsr_densify_plan", dev, P, PLAN_KINDS[kind], int(N), f.data_ptr(), _lib.ptr(pr), plan.data_ptr(), header.data_ptr(),
+         ws.data_ptr(), ws.numel())
+    return plan, header
+
+
+def apply_device_plan(model, plan, header, reset_stats, children=None, merge=None):
+    """apply_plan for a plan that is still on the device (device_plan), with the new rows computed in the same launch
+    (gsr_build_rows).  The one host read of a fused operation happens here: header -> the sizes of the outputs.
+      children = dict(scaling= activated scaling [P, 3], divisor= 0.8 N (split) or 1 (KL clone), unit= N(0, 1) draws [>= n_new, 3]
+                 or None: torch.randn, drawn after the header read): the new rows are children drawn from their source rows
+      merge    = the activated scaling [P, 3]: the new rows are the merged pairs (partners at plan[P:], as device_plan left them)
+    Returns (rows kept, new rows, rows in all)."""
+    dev = model._xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("densify: applying a row plan needs the HIP library (tensors must live on a HIP device)")
+    _need_hip("apply_device_plan", plan, header)
+    n_keep, n_new, n_out, _ = (int(v) for v in header.tolist())
+    if merge is not None and n_new == 0:  # no pair to merge: kl_merge leaves the model as it is, statistics included
+        return n_keep, n_new, n_out
+    P = model._xyz.shape[0]
+    arrays, srcs, outs, widths, zero_new, move = _row_tables(model, n_out, reset_stats)
+    if n_out and move:
+        n = len(move)
+        mode, scal, unit, divisor, partner = _lib.BUILD_MOVE, None, None, 1.0, None
+        if children is not None and n_new:
+            mode, divisor = _lib.BUILD_CHILDREN, float(children["divisor"])
+            scal = children["scaling"].detach().contiguous().float()
+            unit = children.get("unit")
+            unit = torch.randn((n_new, 3), device=dev) if unit is None else unit[:n_new].to(dev).contiguous().float()
+        elif merge is not None:
+            mode, scal = _lib.BUILD_MERGE, merge.detach().contiguous().float()
+            partner = plan[P:P + n_new]
+        roles = []
+        for i in move:
+            kind, name = arrays[i][0], arrays[i][1]
+            role = _ROLES.get(name, _lib.ROW_MEAN if name in MERGE_MEAN else _lib.ROW_COPY) if kind == "param" else _lib.ROW_COPY
+            roles.append(role)
+        src_p = (C.c_void_p * n)(*[srcs[i].data_ptr() for i in move])
+        dst_p = (C.c_void_p * n)(*[outs[i].data_ptr() for i in move])
+        w_p = (C.c_int * n)(*[widths[i] for i in move])
+        z_p = (C.c_int * n)(*[zero_new[i] for i in move])
+        r_p = (C.c_int * n)(*roles)
+        call("gsr_build_rows", dev, n, src_p, dst_p, w_p, z_p, r_p, n_out, plan.data_ptr(), P, n_out - n_new, mode,
+             _lib.ptr(scal), _lib.ptr(unit), divisor, _lib.ptr(partner))
+    _reregister(model, arrays, outs)
+    return n_keep, n_new, n_out
 
 
 # ---------------------------------------------------------------- the reference's operations
@@ -169,11 +301,29 @@ def update_max_radii(model, radii, visibility_filter):
     model.max_radii2D = torch.where(visibility_filter, torch.maximum(model.max_radii2D, r), model.max_radii2D)
 
 
-def prune_points(model, mask):
+def _fused_check(what, model, *tensors):
+    if not model._xyz.is_cuda:
+        raise RuntimeError(f"{what}(fused=True): tensors must live on a HIP device (no CPU path)")
+    _need_hip(f"{what}(fused=True)", *tensors)
+
+
+def prune_points(model, mask, fused=False):
+    """fused: the plan is built on the device (device_plan) instead of by torch.nonzero."""
+    if fused:
+        _fused_check("prune_points", model, mask)
+        plan, header = device_plan("prune", mask)
+        apply_device_plan(model, plan, header, reset_stats=False)
+        return
     apply_plan(model, plan_prune(mask), reset_stats=False)
 
 
-def densify_and_clone(model, grads, grad_threshold, scene_extent):
+def densify_and_clone(model, grads, grad_threshold, scene_extent, fused=False):
+    if fused:
+        _fused_check("densify_and_clone", model, grads)
+        flags = device_select("clone", grads, model.get_scaling.detach(), grad_threshold, model.percent_dense * scene_extent)
+        plan, header = device_plan("clone", flags)
+        apply_device_plan(model, plan, header, reset_stats=True)
+        return flags.view(torch.bool)
     sel = clone_mask(grads, model.get_scaling, grad_threshold, scene_extent, model.percent_dense)
     apply_plan(model, plan_clone(sel), reset_stats=True)
     return sel
@@ -200,8 +350,25 @@ def _split_selected(model, sel, N, unit_samples):
             model._scaling[first:] = new_scaling
 
 
-def densify_and_split(model, grads, grad_threshold, scene_extent, N=2, unit_samples=None):
+def _split_fused(what, model, grads, grad_threshold, scene_extent, kl_threshold, N, unit_samples):
+    """densify_and_split / kl_densify_and_split (kl_threshold not None) as select -> plan -> header read -> build rows."""
+    _fused_check(what, model, grads)
+    scal = model.get_scaling.detach()
+    kl = None
+    if kl_threshold is not None:
+        kl, _ = _kl_to_nearest_fused(model)
+        model.kl_selected_pts_mask = kl > kl_threshold
+    flags = device_select("split", grads, scal, grad_threshold, model.percent_dense * scene_extent, kl,
+                          0.0 if kl_threshold is None else kl_threshold)
+    plan, header = device_plan("split", flags, N=N)
+    apply_device_plan(model, plan, header, reset_stats=True, children=dict(scaling=scal, divisor=0.8 * N, unit=unit_samples))
+    return flags.view(torch.bool)
+
+
+def densify_and_split(model, grads, grad_threshold, scene_extent, N=2, unit_samples=None, fused=False):
     """unit_samples: optional N(0,1) draws [N * n_selected, 3] (tests); default torch.randn like the reference's torch.normal."""
+    if fused:
+        return _split_fused("densify_and_split", model, grads, grad_threshold, scene_extent, None, N, unit_samples)
     sel = split_mask(grads, model._xyz.shape[0], model.get_scaling.detach(), grad_threshold, scene_extent, model.percent_dense)
     _split_selected(model, sel, N, unit_samples)
     return sel
@@ -223,9 +390,35 @@ def kl_div(mu_0, rotation_0_q, scaling_0_diag, mu_1, rotation_1_q, scaling_1_dia
     return 0.5 * (trace + maha + logdet - 3.0)
 
 
-def kl_to_nearest(model):
-    """(kl [P], ids [P, 2] int64): divergence between every Gaussian's k-NN pair (:573-589)."""
+def kl_pairs(xyz, rotation, log_scaling, pairs):
+    """kl [P] of the pairs [P, 2] (int32) from the RAW parameters, by one kernel (gsr_kl_pairs): kl_div in the frame of the
+    second Gaussian, without gathers or [P,3,3] temporaries."""
+    _need_hip("kl_pairs", xyz, rotation, log_scaling, pairs)
+    P, dev = xyz.shape[0], xyz.device
+    kl = torch.empty((P,), dtype=torch.float32, device=dev)
+    if P:
+        x, r, s = (t.detach().contiguous().float() for t in (xyz, rotation, log_scaling))
+        pr = pairs.detach().to(torch.int32).contiguous()
+        call("gsr_kl_pairs", dev, P, x.data_ptr(), r.data_ptr(), s.data_ptr(), pr.data_ptr(), kl.data_ptr())
+    return kl
+
+
+def _kl_to_nearest_fused(model):
+    """kl_to_nearest on the raw parameters; ids stay int32 as the k-NN returns them."""
     from .knn_cuda import knn_self
+    _fused_check("kl_to_nearest", model)
+    xyz = model._xyz.detach()
+    _, ids = knn_self(xyz, 2)
+    return kl_pairs(xyz, model._rotation, model._scaling, ids), ids
+
+
+def kl_to_nearest(model, fused=False):
+    """(kl [P], ids [P, 2] int64): divergence between every Gaussian's k-NN pair (:573-589).  fused: one kernel (gsr_kl_pairs) on
+    the raw rotation and log-scaling instead of kl_div on gathered rows."""
+    from .knn_cuda import knn_self
+    if fused:
+        kl, ids = _kl_to_nearest_fused(model)
+        return kl, ids.long()
     xyz = model._xyz.detach()
     _, ids = knn_self(xyz, 2)
     ids = ids.long()
@@ -234,8 +427,17 @@ def kl_to_nearest(model):
     return kl_div(xyz[i0], rot[i0], scal[i0], xyz[i1], rot[i1], scal[i1]), ids
 
 
-def kl_densify_and_clone(model, grads, grad_threshold, scene_extent, kl_threshold=0.4, unit_samples=None):
+def kl_densify_and_clone(model, grads, grad_threshold, scene_extent, kl_threshold=0.4, unit_samples=None, fused=False):
     """:566-606.  Unlike densify_and_clone the copy is displaced by a draw from the Gaussian itself."""
+    if fused:
+        _fused_check("kl_densify_and_clone", model, grads)
+        scal = model.get_scaling.detach()
+        kl, _ = _kl_to_nearest_fused(model)
+        model.kl_selected_pts_mask = kl > kl_threshold
+        flags = device_select("clone", grads, scal, grad_threshold, model.percent_dense * scene_extent, kl, kl_threshold)
+        plan, header = device_plan("clone", flags)
+        apply_device_plan(model, plan, header, reset_stats=True, children=dict(scaling=scal, divisor=1.0, unit=unit_samples))
+        return flags.view(torch.bool)
     sel = clone_mask(grads, model.get_scaling.detach(), grad_threshold, scene_extent, model.percent_dense)
     kl, _ = kl_to_nearest(model)
     model.kl_selected_pts_mask = kl > kl_threshold
@@ -256,8 +458,10 @@ def kl_densify_and_clone(model, grads, grad_threshold, scene_extent, kl_threshol
     return sel
 
 
-def kl_densify_and_split(model, grads, grad_threshold, scene_extent, kl_threshold=0.4, N=2, unit_samples=None):
+def kl_densify_and_split(model, grads, grad_threshold, scene_extent, kl_threshold=0.4, N=2, unit_samples=None, fused=False):
     """:608-666."""
+    if fused:
+        return _split_fused("kl_densify_and_split", model, grads, grad_threshold, scene_extent, kl_threshold, N, unit_samples)
     sel = split_mask(grads, model._xyz.shape[0], model.get_scaling.detach(), grad_threshold, scene_extent, model.percent_dense)
     kl, _ = kl_to_nearest(model)
     model.kl_selected_pts_mask = kl > kl_threshold
@@ -266,13 +470,22 @@ def kl_densify_and_split(model, grads, grad_threshold, scene_extent, kl_threshol
     return sel
 
 
-def kl_merge(model, grads, grad_threshold, scene_extent, kl_threshold=0.1):
+def kl_merge(model, grads, grad_threshold, scene_extent, kl_threshold=0.1, fused=False):
     """:668-708: a selected small Gaussian whose pair is closer than kl_threshold is replaced, together with its partner, by one
     Gaussian at their mean (position, SH, opacity averaged; rotation of the first, its scale / 0.8).
 
     The reference's body cannot run as written: it averages `_normal[selected_pts_mask]` over the wrong axis and calls
     densification_postfix with 7 of its 9 arguments (:694-698, a TypeError).  normal / albedo / roughness follow the rule of the
     other averaged attributes here (mean over the pair)."""
+    if fused:
+        _fused_check("kl_merge", model, grads)
+        scal = model.get_scaling.detach()
+        kl, ids = _kl_to_nearest_fused(model)
+        model.kl_selected_pts_mask = kl < kl_threshold
+        flags = device_select("merge", grads, scal, grad_threshold, model.percent_dense * scene_extent, kl, kl_threshold)
+        plan, header = device_plan("merge", flags, pairs=ids)
+        apply_device_plan(model, plan, header, reset_stats=True, merge=scal)
+        return flags.view(torch.bool)
     P = model._xyz.shape[0]
     padded = torch.zeros((P,), device=grads.device, dtype=grads.dtype)
     padded[:grads.shape[0]] = grads.squeeze()
@@ -314,13 +527,20 @@ def reset_opacity(model):
     model._opacity = new
 
 
-def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, t_vertices=None, unit_samples=None):
-    """scene/gaussian_model.py:697-726 (the KL variants are commented out in the reference)."""
+def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, t_vertices=None, unit_samples=None,
+                      kl_threshold=None, fused=False):
+    """scene/gaussian_model.py:697-726.  kl_threshold: a number runs kl_densify_and_clone / kl_densify_and_split with it instead
+    of the plain clone and split (the reference's commented-out lines :702-703); None = the reference's sequence.
+    fused: every operation of the sequence with fused=True."""
     from .knn_cuda import knn_nearest
     grads = model.xyz_gradient_accum / model.denom
     grads[grads.isnan()] = 0.0
-    densify_and_clone(model, grads, max_grad, extent)
-    densify_and_split(model, grads, max_grad, extent, unit_samples=unit_samples)
+    if kl_threshold is None:
+        densify_and_clone(model, grads, max_grad, extent, fused=fused)
+        densify_and_split(model, grads, max_grad, extent, unit_samples=unit_samples, fused=fused)
+    else:
+        kl_densify_and_clone(model, grads, max_grad, extent, kl_threshold=kl_threshold, unit_samples=unit_samples, fused=fused)
+        kl_densify_and_split(model, grads, max_grad, extent, kl_threshold=kl_threshold, unit_samples=unit_samples, fused=fused)
     prune_mask = (model.get_opacity < min_opacity).squeeze()
     if max_screen_size:
         big_points_vs = model.max_radii2D > max_screen_size
@@ -329,5 +549,5 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, t_v
     if t_vertices is not None:  # use the SMPL prior to prune points (:715-720)
         distance, _ = knn_nearest(t_vertices.reshape(-1, 3), model._xyz.detach())
         prune_mask = prune_mask | (distance > 0.05)
-    prune_points(model, prune_mask)
+    prune_points(model, prune_mask, fused=fused)
     return prune_mask
