@@ -15,6 +15,10 @@ Rules of a captured region (violations bake a stale pointer or an unqueryable ob
   * no pinned status words / event records (fastpath.DeferredStatus): rasterize_gaussians_async notices the capture, writes its
     (R, flags) into a device tensor and leaves its deferred overflow watch out (AsyncCapacity.graph_status keeps those tensors
     for check());
+  * a replay runs no host code: no tensor's `_version` moves, whatever the replay writes (a recorded optimizer step included), so
+    nothing derived from tensors a replay writes may be cached under their version;
+  * the vertex grid and the nearest-vertex cache of the big-pose vertices (lbs._GRIDS) are looked up when the frame is RECORDED: a
+    captured frame is bound to the values of the big-pose vertices it was recorded with (one subject: the same for every camera);
   * the number of Gaussians is baked in: capture again after a densification / pruning step;
   * the active SH degree (pc.active_sh_degree) and the scale modifier are by-value kernel arguments as well: a captured frame
     keeps rendering the degree it was recorded at -- capture again after oneupSHdegree();

@@ -94,7 +94,11 @@ class _FrameConstants:
     posedirs / shapedirs / J_regressor invalidates the entry); the entry keeps the inputs alive, so an address cannot be handed
     to different data while the entry lives.  Bypassed -- plain recomputation -- for inputs inside the autograd graph, for
     inference tensors (they have no version counter) and while a stream is being captured into a graph (memory of a graph's
-    private pool must not end up in a process-wide cache).  LRU, a few hundred entries: two per (camera, subject) pair."""
+    private pool must not end up in a process-wide cache).  LRU, a few hundred entries: two per (camera, subject) pair.
+    The version in the key is sound because only torch ops write these inputs (dataset code, `copy_` into a captured frame's static
+    tensors): no kernel of this package is handed their address to write, and no optimizer owns them.  It would NOT be sound for
+    anything derived from trained parameters -- optim.FusedAdam's kernels bump the version only from host code, a graph replay
+    not at all (nets.FusedLBSOffsetDecoder packs its weights on every call for that reason)."""
 
     def __init__(self, capacity=256):
         from collections import OrderedDict
@@ -210,7 +214,10 @@ class _VertexGridCache:
     """Grid workspaces of reference-vertex tensors that were seen before.  The big-pose vertices of a subject are the same
     tensor frame after frame (one per camera, scene/cameras.py:72), so their 46 us single-workgroup grid build is done once.
     Key = (storage address, tensor version, shape): any in-place change bumps the version; the entry holds a reference to the
-    tensor, so its address cannot be handed to another tensor while the entry lives.  Memory: ~0.7 MB per entry, LRU."""
+    tensor, so its address cannot be handed to another tensor while the entry lives.  Memory: ~0.7 MB per entry, LRU.
+    The vertices are dataset tensors that only torch ops write (never a parameter, never an output of this package's kernels), so
+    the version tells the truth in eager code.  While a frame is being captured the lookup happens once, at record time: the
+    recorded frame skips the build and trusts the nearest-vertex cache for the VALUES it was recorded with (graph.py's rules)."""
 
     def __init__(self, capacity=1024):
         from collections import OrderedDict

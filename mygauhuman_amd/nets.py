@@ -10,6 +10,8 @@ spends in skinny fp32 GEMMs and 100-MB elementwise kernels.  Here forward() is O
 in registers, the accuracy of the torch ops) and the backward two (the forward again + dh = W^T dZ chained the same way; the
 weight gradients as products over the points).  render() hands the positions in DETACHED (:104): a `pts` that requires grad takes
 the same arithmetic in torch ops instead (forward_torch).  Tensors must live on the GPU: there is no CPU path for the fused kernels.
+Every fused forward -- with or without grad -- packs the weights it runs on from the live parameters: no packed copy outlives a call
+as a cache, so an optimizer kernel that writes the parameters behind torch's back, or a graph replay, cannot leave a stale one.
 
 The fused kernels are built for the bone counts in FUSED_BONE_COUNTS: SMPL's 24 and SMPL-X's 55 (csrc/mlp.hip packs the output
 layer as one or two 32-row tiles).  FusedLBSOffsetDecoder switches them on by default at 24 only; at 55 set use_fused, or use
@@ -44,7 +46,7 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
     # class-level defaults: a module restored by pickle without them (GaussianModel.capture() pickles the decoder; __getstate__
     # drops the device-side cache) still runs
     use_fused = False
-    _packed, _packed_key = None, None
+    _packed, _packed_key = None, None   # (_packed_key: what earlier versions keyed the buffer on; nothing reads it any more)
 
     def __init__(self, total_bones=24):
         super().__init__()
@@ -55,13 +57,13 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
         self.bw_linears = torch.nn.ModuleList([torch.nn.Conv1d(E, W, 1), torch.nn.Conv1d(W, W, 1), torch.nn.Conv1d(W, W, 1),
                                                torch.nn.Conv1d(W + E, W, 1)])
         self.bw_fc = torch.nn.Conv1d(W, total_bones, 1)
-        self._packed, self._packed_key = None, None
+        self._packed = None
         # False: the same arithmetic in torch ops (forward_torch), for comparison -- and the only path outside FUSED_BONE_COUNTS
         self.use_fused = total_bones == self.FUSED_BONES
 
     def __getstate__(self):
         state = super().__getstate__().copy()
-        state.pop("_packed", None)       # a device buffer derived from the parameters: re-packed on the first fused call
+        state.pop("_packed", None)       # a device buffer derived from the parameters: allocated again on the first fused call
         state.pop("_packed_key", None)
         return state
 
@@ -69,17 +71,20 @@ class FusedLBSOffsetDecoder(torch.nn.Module):
         return list(self.bw_linears) + [self.bw_fc]
 
     def _packed_weights(self, dev):
-        """The A fragments of the five layers, re-packed whenever a parameter changed (in-place updates bump `_version`)."""
+        """The A fragments of the five layers, packed from the LIVE parameters on every call (one small launch) into the module's
+        persistent buffer.  Nothing is keyed on the parameters' `_version`: a kernel that is handed their data_ptr() (optim.FusedAdam)
+        and every replay of a captured optimizer step rewrite them without any host code that could bump it.  The buffer is
+        allocated once per device, so a recorded forward replays the pack with the weights of that replay; one allocated while a
+        stream is being captured belongs to that graph's pool and is not kept."""
         ts = [t for m in self._layers() for t in (m.weight, m.bias)]
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(dev),)
-        if self._packed is None or self._packed_key != key:
-            for t in ts:
-                if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                    raise RuntimeError("FusedLBSOffsetDecoder: parameters must be contiguous float32 tensors on a HIP device")
-            self._packed = _pack(self.total_bones, ts, dev,
-                                 None if (self._packed is None or self._packed.device != dev) else self._packed)
-            self._packed_key = key
-        return self._packed
+        for t in ts:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError("FusedLBSOffsetDecoder: parameters must be contiguous float32 tensors on a HIP device")
+        own = self._packed if (self._packed is not None and self._packed.device == dev) else None
+        packed = _pack(self.total_bones, ts, dev, own)
+        if packed is not own and not torch.cuda.is_current_stream_capturing():
+            self._packed = packed
+        return packed
 
     def forward_torch(self, pts):
         """The reference's arithmetic in torch ops (row-major linear layers on [P, C]); differentiable."""

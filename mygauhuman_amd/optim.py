@@ -14,7 +14,12 @@ What differs underneath:
     `cubemap.clamp_(min=0.0)` after the light step;
   * the launch table (pointers of parameter, gradient and both moments) is cached and rebuilt whenever one of those tensors has
     been replaced -- a host-side comparison of data_ptr()s, no device read.  A gradient that is not contiguous is replaced by a
-    contiguous copy once (p.grad is reassigned; rare: autograd hands out contiguous gradients for contiguous leaves).
+    contiguous copy once (p.grad is reassigned; rare: autograd hands out contiguous gradients for contiguous leaves);
+  * the kernels write the parameters, both moments and the statistics through their data_ptr()s, so step() and update_stats()
+    bump the version counter of every tensor a launch wrote (torch.autograd.graph.increment_version: host-only, nothing is
+    launched): a backward over values saved before the step raises as it does after torch's step, and caches keyed on `_version`
+    see the write.  A step recorded into a graph bumps once, at record time; a REPLAY runs no host code and bumps nothing, so
+    nothing derived from tensors a replay writes may be keyed on their version.
 
 There is no CPU path: step() on CPU parameters raises.
 """
@@ -113,6 +118,12 @@ def update_stats(model, viewspace_point_tensor, update_filter, radii, debug=Fals
     st, keep = _stats_block(model, viewspace_point_tensor, update_filter, radii)
     dev = keep[3].device
     call("gsr_stats_update", dev, C.byref(st), int(debug))
+    _written(keep[3:])
+
+
+def _written(tensors):
+    """Tell torch that a kernel wrote these tensors in place (host-only; legal while a stream is being captured)."""
+    torch.autograd.graph.increment_version(tensors)
 
 
 class FusedAdam(torch.optim.Adam):
@@ -139,6 +150,7 @@ class FusedAdam(torch.optim.Adam):
         self._lr_table = None
         self._key = None          # what the cached launch tables were built from
         self._launches = []
+        self._writes = []         # the tensors those launches write in place: parameters and both moments
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0, amsgrad=False, foreach=False, maximize=False,
                          capturable=False, differentiable=False, fused=True)
 
@@ -296,6 +308,7 @@ class FusedAdam(torch.optim.Adam):
         if not items:
             if st_block is not None:
                 call("gsr_stats_update", keep[3].device, C.byref(st_block), int(self._debug))
+                _written(keep[3:])
             return loss
         dev = items[0][0].device
         key = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(),
@@ -304,6 +317,8 @@ class FusedAdam(torch.optim.Adam):
             if any(p.device != dev for p, _, _, _ in items) or self._steps.device != dev:
                 raise RuntimeError("FusedAdam.step: all parameters (and the step table) must be on one device")
             self._launches = self._build(items)
+            # (the step table is written too, but only the kernels read it)
+            self._writes = [t for p, _, st, _ in items for t in (p, st["exp_avg"], st["exp_avg_sq"])]
             self._key = key
         capturing = torch.cuda.is_current_stream_capturing()
         if capturing and (self._lr_table is None or self._lr_table.numel() < len(self.param_groups)):
@@ -319,4 +334,5 @@ class FusedAdam(torch.optim.Adam):
             last = n == len(self._launches) - 1
             call("gsr_adam_step", dev, len(arr), arr, len(grp), grp, lr_ptr, self._steps.data_ptr(),
                  C.byref(st_block) if (st_block is not None and last) else None, int(self._debug))
+        _written(self._writes if st_block is None else self._writes + list(keep[3:]))
         return loss
