@@ -1,7 +1,7 @@
 // bake.hip -- per-Gaussian ambient occlusion bake (baking.py bake_set).
 //
 // Built with -ffp-contract=off like geometry.hip, so the projection (project.h) gives the rasterizer's preprocess bits; the
-// blend step turns contraction back on locally, as blend_fwd.hip is built, so that its arithmetic is written the same way.
+// blend step is the contribution rule of blend_common.h, which turns contraction back on locally, as the blend files are built.
 //
 //   grid       pc_to_grid(points, 10): bounding box, cell index per point, the occupied cells compacted in (ix, iy, iz)
 //              lexicographic order (torch.unique's order), centres min + idx * size + size / 2
@@ -14,7 +14,7 @@
 //   env reduce clamp(sum_hw clamp(occ, 0, 1) * env[hw], 0, 1) per Gaussian, three copies
 #include <vector>
 
-#include "gsr_common.h"
+#include "blend_common.h"
 #include "project.h"
 
 namespace gsr {
@@ -295,20 +295,18 @@ __global__ __launch_bounds__(1024) void bake_scan_kernel(const uint32_t *counts,
   }
 }
 
-// blend_fwd.hip's step for one pixel and one list entry, written the same way and with contraction on as that file is built
-__device__ __forceinline__ void bake_blend_step(float gx, float gy, float qa, float qb, float qc, float l255, float o, float px, float py,
-                                                float &T, float &Wt, float &dbias) {
+// the blend forward's step for one pixel and one list entry (rows g0 = x, y, qa, qb; g1 = qc, log2(255 o), o): the contribution
+// rule of blend_common.h, with contraction on as the blend files are built
+__device__ __forceinline__ void bake_blend_step(float4 g0, float4 g1, float px, float py, float &T, float &Wt, float &dbias) {
 #pragma clang fp contract(fast)
-  const float dx = gx - px, dy = gy - py;
-  const float p2 = dx * (qa * dx + qb * dy) + (qc * dy) * dy;  // power * log2(e)
-  const bool pre = !(p2 > 0.0f) && ((p2 + l255) >= dbias);
-  if (!pre) return;
-  const float alpha = fminf(0.99f, o * __builtin_amdgcn_exp2f(p2));
-  const bool hit = !(alpha < 1.0f / 255.0f);
+  float pw;
+  if (!cutoff_pre(g0, g1, px, py, dbias, pw)) return;
+  const float alpha = blend_alpha(g1.z, pw);
+  const bool hit = !(alpha < ALPHA_MIN);
   const float test_T = T * (1.0f - alpha);
-  const bool stop = hit && test_T < 0.0001f;
+  const bool stop = hit && test_T < T_MIN;
   const bool blend = hit && !stop;
-  dbias = stop ? 1e30f : dbias;
+  dbias = stop ? CUT_DONE : dbias;
   const float w = blend ? alpha * T : 0.0f;
   Wt += w;
   T = blend ? test_T : T;
@@ -336,7 +334,7 @@ __global__ __launch_bounds__(WAVE) void bake_blend_kernel(const BakeArgs a, int 
     pyf[s] = (float)(pid[s] >= 0 ? pid[s] / BK_N : 0);
     T[s] = 1.0f;
     Wt[s] = 0.0f;
-    dbias[s] = pid[s] >= 0 ? -0.02f : 1e30f;
+    dbias[s] = pid[s] >= 0 ? CUT_LIVE : CUT_DONE;
   }
   const uint2 r = ranges[t];
   constexpr float L2E = 1.4426950408889634f;
@@ -355,14 +353,12 @@ __global__ __launch_bounds__(WAVE) void bake_blend_kernel(const BakeArgs a, int 
       s0[lane] = make_float4(pr.x, pr.y, (-0.5f * L2E) * pr.ca, -L2E * pr.cb);
       s1[lane] = make_float4((-0.5f * L2E) * pr.cc, __builtin_amdgcn_logf(255.0f * o), o, 0.0f);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int cnt = (int)min((uint32_t)WAVE, r.y - base);
     for (int k = 0; k < cnt; k++) {
       const float4 g0 = s0[k], g1 = s1[k];
 #pragma unroll
-      for (int s = 0; s < 4; s++) bake_blend_step(g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, pxf[s], pyf[s], T[s], Wt[s], dbias[s]);
+      for (int s = 0; s < 4; s++) bake_blend_step(g0, g1, pxf[s], pyf[s], T[s], Wt[s], dbias[s]);
     }
     __builtin_amdgcn_wave_barrier();
   }

@@ -15,15 +15,9 @@
 // row r's Gaussian into that Gaussian's packed 64-byte gradient row (GROW floats: one memory-side request per
 // Gaussian row instead of 9 scattered ones).  Ballots skip the exp / the reduction / the atomics whenever no lane
 // is hit.
-#include "gsr_common.h"
+#include "blend_common.h"
 
 namespace gsr {
-
-__device__ __forceinline__ uint32_t xcd_remap_b(uint32_t bid, uint32_t n) {
-  const uint32_t q = n / 8, r = n % 8, xcd = bid % 8, k = bid / 8;
-  const uint32_t start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return start + k;
-}
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
@@ -136,12 +130,11 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
   if constexpr (WPT == 4) {
     const int omode = tile_order_mode(a.order);
     const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
-    const uint32_t item = omode ? ordered_item4(blockIdx.x, n_slots) : (blockIdx.x < n_slots * 4u ? xcd_remap_b(blockIdx.x, n_slots * 4u) : n_slots * 4u);
-    const uint32_t entry = tile_of_slot(a.order, omode, item / 4u, n_slots);
+    const uint32_t entry = entry_of_quadrant_workgroup(a.order, omode, n_slots, part);
     if (entry == ORDER_NO_TILE) return;  // (wave-uniform) padding slot, or beyond this frame's slots
-    tile = order_entry_tile(entry), seg = order_entry_seg(entry), nseg = order_entry_nseg(entry), part = item % 4u;
+    tile = order_entry_tile(entry), seg = order_entry_seg(entry), nseg = order_entry_nseg(entry);
   } else {
-    const uint32_t item = xcd_remap_b(blockIdx.x, gridDim.x);  // (fewer waves per tile: natural order)
+    const uint32_t item = xcd_remap(blockIdx.x, gridDim.x);  // (fewer waves per tile: natural order)
     tile = item / WPT, part = item % WPT;
   }
   const int tx = tile % a.grid_x, ty = tile / a.grid_x;
@@ -249,9 +242,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
     s_rw[lane * 4 + 0] = dpix0[0];
     s_rw[lane * 4 + 1] = dpix1[0];
     s_rw[lane * 4 + 2] = dpix2[0];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const float4 t4 = *reinterpret_cast<const float4 *>(&s_rw[((lane & 15) + 16 * q) * 4]);
@@ -303,9 +294,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
         for (int q = 0; q < CE / 2; q++) reinterpret_cast<float2 *>(&s_x[slot * CE])[q] = xs[q];
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     for (int g = 0; g < cnt; g += 4) {
       float acc[4][NA];
@@ -328,16 +317,17 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
           const int fpos = (int)__float_as_uint(g1.z);  // 0-based position from the front
 #pragma unroll
           for (int s = 0; s < SLOTS; s++) {
+            // (cutoff_pre_replay of blend_common.h, written out: dx and dy also enter the moments below)
             const float dx = g0.x - pxf[s], dy = g0.y - pyf[s];
             const float p2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;  // power * log2(e)
-            const bool pre = (fpos < lastc[s]) && !(p2 > 0.0f) && (p2 + g1.y >= -0.02f);
+            const bool pre = (fpos < lastc[s]) && !(p2 > 0.0f) && (p2 + g1.y >= CUT_LIVE);
             if (__ballot(pre) != 0ull) {  // wave-uniform: some lane may reach alpha >= 1/255
               // Select form instead of an exec-masked block: on lanes that are not hit alpha and G are forced to zero, which
               // makes every update below an exact no-op (rc = 1, Tn = T, w = 0, r = 0) -- same results, no second ballot,
               // no mask save / restore, no zero-initialisation of the sums.
-              const float G0 = __builtin_amdgcn_exp2f(p2);
-              const float alpha0 = fminf(0.99f, g1.w * G0);
-              const bool hit = pre && !(alpha0 < 1.0f / 255.0f);
+              float G0;
+              const float alpha0 = blend_alpha(g1.w, p2, G0);
+              const bool hit = pre && !(alpha0 < ALPHA_MIN);
               const float alpha = hit ? alpha0 : 0.f, G = hit ? G0 : 0.f;
               const float rc = __builtin_amdgcn_rcpf(1.f - alpha);
               const float Tn = T[s] * rc;  // transmittance in front of this Gaussian
@@ -413,9 +403,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
           if constexpr (LFOLD) {
             *reinterpret_cast<float4 *>(&s_rw[lane * LROW]) = make_float4(acc[0][0], acc[0][1], acc[1][0], acc[1][1]);
             *reinterpret_cast<float4 *>(&s_rw[lane * LROW + 4]) = make_float4(acc[2][0], acc[2][1], acc[3][0], acc[3][1]);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             float2 rw[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) rw[q] = *reinterpret_cast<const float2 *>(&s_rw[((int)(lane & 15) + 16 * q) * LROW + 2 * row]);
@@ -487,9 +475,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_kernel(const BlendBwdArgs
             t2[16] = qc;
             t2[24] = ka;
             t2[32] = kb;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             // column k: 0 r dx (lower qb) 1 r dy (upper qa) 2 r dx^2 (lower qc) 3 r dx dy (upper qb) 4 r dy^2 (upper qc)
             //           5 r (lower qa)    6 red (lower ka)  7 green (upper ka)   8 blue (lower kb)
             constexpr uint64_t HALF_OF_K = 0x000000000000009Aull;                  // bit k: upper half
@@ -650,12 +636,12 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
   const uint32_t rw_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)s_rw);  // LDS byte address of the reduction buffer
 
   const unsigned long long trace_t0 = a.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  uint32_t part;
   const int omode = tile_order_mode(a.order);
   const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
-  const uint32_t item = omode ? ordered_item4(blockIdx.x, n_slots) : (blockIdx.x < n_slots * 4u ? xcd_remap_b(blockIdx.x, n_slots * 4u) : n_slots * 4u);
-  const uint32_t entry = tile_of_slot(a.order, omode, item / 4u, n_slots);
+  const uint32_t entry = entry_of_quadrant_workgroup(a.order, omode, n_slots, part);
   if (entry == ORDER_NO_TILE) return;  // (wave-uniform) padding slot, or beyond this frame's slots
-  const uint32_t tile = order_entry_tile(entry), seg = order_entry_seg(entry), nseg = order_entry_nseg(entry), part = item % 4u;
+  const uint32_t tile = order_entry_tile(entry), seg = order_entry_seg(entry), nseg = order_entry_nseg(entry);
   const int tx = tile % a.grid_x, ty = tile / a.grid_x;
   const uint32_t lane = threadIdx.x;
   const uint2 range = a.ranges[tile];
@@ -725,9 +711,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
   s_rw[lane] = dpix0;
   s_rw[WAVE + lane] = dpix1;
   s_rw[2 * WAVE + lane] = dpix2;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 #pragma unroll
   for (int ch = 0; ch < 3; ch++) {
     const float4 t4 = *reinterpret_cast<const float4 *>(&s_rw[ch * WAVE + kcol * 4u]);
@@ -796,9 +780,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
       s2[slot] = make_float4(r1.w, r2.x, r2.y, r1.z);
       s_id[slot] = id * (uint32_t)(GROW * sizeof(float));  // (P < 2^25: gsr_rasterize_backward refuses more)
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // byte offset of the group's first survivor row (and of this reducer row's id): wave-uniform in fact, kept in VGPRs (the asm
     // hides that from the compiler, which would otherwise move the scalar address into a VGPR in front of every LDS read)
@@ -815,17 +797,16 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
           float4 g1 = lds_at<float4>(s1, vg + 16u * u);
           keep_whole(g1);
           const int fpos = (int)__float_as_uint(g1.z);  // 0-based position from the front
-          const float dx = g0.x - pxf, dy = g0.y - pyf;
-          const float p2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;  // power * log2(e)
-          const bool pre = (fpos < lastc) && !(p2 > 0.0f) && (p2 + g1.y >= -0.02f);
+          float p2;
+          const bool pre = cutoff_pre_replay(g0, g1, pxf, pyf, fpos, lastc, p2);
           if (__ballot(pre) != 0ull) {  // wave-uniform: some lane may reach alpha >= 1/255
             // select form: on lanes that are not hit alpha and G are forced to zero, which makes every update below an exact no-op
             // (rc = 1, Tn = T, w = 0, r = 0)
             float4 g2 = lds_at<float4>(s2, vg + 16u * u);
             keep_whole(g2);
-            const float G0 = __builtin_amdgcn_exp2f(p2);
-            const float alpha0 = fminf(0.99f, g1.w * G0);
-            const bool hit = pre && !(alpha0 < 1.0f / 255.0f);
+            float G0;
+            const float alpha0 = blend_alpha(g1.w, p2, G0);
+            const bool hit = pre && !(alpha0 < ALPHA_MIN);
             const float alpha = hit ? alpha0 : 0.f, G = hit ? G0 : 0.f;
             const float rc = __builtin_amdgcn_rcpf(1.f - alpha);
             const float Tn = T * rc;  // transmittance in front of this Gaussian
@@ -867,9 +848,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
             :
             : "v"(ar[0]), "v"(ar[1]), "v"(ar[2]), "v"(ar[3]), "v"(aw[0]), "v"(aw[1]), "v"(aw[2]), "v"(aw[3]), "s"(rw_base)
             : "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const float4 r4 = *rd_r, w4 = *rd_w;
         __builtin_amdgcn_wave_barrier();  // the second hop's stores stay behind these reads
         // this lane's four pixels: column kcol & 7, rows ly = 2 q + h, h = kcol >> 3
@@ -906,9 +885,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_lds_kernel(const BlendBwd
             : "v"(qa), "v"(qb), "v"(qc), "v"(ka), "v"(kb), "s"(rw_base), "n"(H2_QA * 4), "n"(H2_QB * 4), "n"(H2_QC * 4), "n"(H2_KA * 4),
               "n"(H2_KB * 4)
             : "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const float4 lo4 = src8[0], hi4 = src8[1];
         __builtin_amdgcn_wave_barrier();  // the next group's hop-1 stores stay behind these reads
         const float vsum = ((lo4.x + lo4.y) + (lo4.z + lo4.w)) + ((hi4.x + hi4.y) + (hi4.z + hi4.w));
@@ -958,10 +935,10 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
   __shared__ float4 s2[WAVE];     // g, b, log2(255*opacity), front position (bits)
   __shared__ uint32_t s_id[WAVE + 4];
 
+  uint32_t part;
   const int omode = tile_order_mode(a.order);
   const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
-  const uint32_t item = omode ? ordered_item4(blockIdx.x, n_slots) : (blockIdx.x < n_slots * 4u ? xcd_remap_b(blockIdx.x, n_slots * 4u) : n_slots * 4u);
-  const uint32_t entry = tile_of_slot(a.order, omode, item >> 2, n_slots), part = item & 3;
+  const uint32_t entry = entry_of_quadrant_workgroup(a.order, omode, n_slots, part);
   if (entry == ORDER_NO_TILE || order_entry_seg(entry) != 0u) return;  // (this variant walks a cut list whole, from its first segment's slot)
   const uint32_t tile = order_entry_tile(entry);
   const int tx = tile % a.grid_x, ty = tile / a.grid_x;
@@ -999,9 +976,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
   s_t[lane] = dpix0;
   s_t[64 + lane] = dpix1;
   s_t[128 + lane] = dpix2;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   float bw[16];
 #pragma unroll
   for (int t = 0; t < 16; t++) {
@@ -1059,9 +1034,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
       s2[slot] = make_float4(r2.x, r2.y, __builtin_amdgcn_logf(255.0f * r1.y), __uint_as_float((uint32_t)(n - 1 - idx)));
       s_id[slot] = id;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     for (int g = 0; g < cnt; g += MG) {
       const int ng = min(MG, cnt - g);
@@ -1073,11 +1046,11 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
         const int fpos = (int)__float_as_uint(g2.w);  // 0-based position from the front
         const float dx = g0.x - pxf, dy = g0.y - pyf;
         const float p2 = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;  // power * log2(e)
-        const bool pre = (fpos < lastc) && !(p2 > 0.0f) && (p2 + g2.z >= -0.02f);
+        const bool pre = (fpos < lastc) && !(p2 > 0.0f) && (p2 + g2.z >= CUT_LIVE);  // (cutoff_pre_replay on this kernel's own row layout)
         if (__ballot(pre) != 0ull) {
-          const float G = __builtin_amdgcn_exp2f(p2);
-          const float alpha = fminf(0.99f, g1.y * G);
-          const bool hit = pre && !(alpha < 1.0f / 255.0f);
+          float G;
+          const float alpha = blend_alpha(g1.y, p2, G);
+          const bool hit = pre && !(alpha < ALPHA_MIN);
           if (__ballot(hit) != 0ull) {
             float r = 0.f, w = 0.f;
             if (hit) {  // exec-masked body: state changes on hit lanes only
@@ -1097,9 +1070,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
         }
       }
       if (anyhit) {  // wave-uniform
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         const float4 a0 = arow[0], a1v = arow[1], a2 = arow[2], a3 = arow[3];
         f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};  // two chains: a dependent MFMA waits 40 cycles, an independent one 32
         d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, bw[0], d0, 0, 0, 0);
@@ -1125,9 +1096,7 @@ __global__ __launch_bounds__(WAVE) void blend_backward_mfma_kernel(const BlendBw
 #pragma unroll
           for (int r = 0; r < 4; r++) s_t[(4 * mk + r) * 16 + mi] = d0[r];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int R = 4 * (mk & 1) + r;  // survivor of the group this lane's register r belongs to
@@ -1218,10 +1187,10 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
   static_assert(FX_LROW % 2 == 0 && FX_LROW >= 8, "hop 1 stores four (r, w) pairs per lane, read back as float2");
   const unsigned long long trace_t0 = a.trace ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
+  uint32_t part;
   const int omode = tile_order_mode(a.order);
   const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
-  const uint32_t item = omode ? ordered_item4(blockIdx.x, n_slots) : (blockIdx.x < n_slots * 4u ? xcd_remap_b(blockIdx.x, n_slots * 4u) : n_slots * 4u);
-  const uint32_t entry = tile_of_slot(a.order, omode, item / 4, n_slots), part = item % 4;
+  const uint32_t entry = entry_of_quadrant_workgroup(a.order, omode, n_slots, part);
   if (entry == ORDER_NO_TILE) return;
   const uint32_t tile = order_entry_tile(entry), seg = order_entry_seg(entry), nseg = order_entry_nseg(entry);
   const int tx = tile % a.grid_x, ty = tile / a.grid_x;
@@ -1323,9 +1292,7 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
   const int row = (int)(lane >> 4), kcol = (int)(lane & 15);
   const bool upper = (lane & 8u) != 0;
   const int jj = (int)(lane & 7u);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();  // (the table is complete before any reducer lane reads it)
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();  // (the table is complete before any reducer lane reads it)
 
   // FULL_ROWS: the whole row (cut-off test, colour, 18 channels = 32 registers) is fetched a survivor ahead: no exposed LDS round
   // trip, 160 VGPRs = three waves per SIMD.  Otherwise only the cut-off rows travel ahead and a contributing survivor fetches its
@@ -1389,9 +1356,7 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
           }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
       const int m = min(FB, cnt - h0);
       // The survivors' LDS rows travel through registers ONE SURVIVOR AHEAD of the arithmetic (two register sets, A and B, used in
       // turn: A always holds the first survivor of a group).  A wave's walk is a dependent chain and the kernel lasts as long as its
@@ -1409,15 +1374,14 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
         }
         auto one = [&](Row &r, int u) {
           const int fpos = (int)__float_as_uint(r.g1.z);  // 0-based position from the front
-          const float dx = r.g0.x - pxf, dy = r.g0.y - pyf;
-          const float p2 = dx * (r.g0.z * dx + r.g0.w * dy) + (r.g1.x * dy) * dy;  // power * log2(e)
-          const bool pre = (fpos < lastc) && !(p2 > 0.0f) && (p2 + r.g1.y >= -0.02f);
+          float p2;
+          const bool pre = cutoff_pre_replay(r.g0, r.g1, pxf, pyf, fpos, lastc, p2);
           if (__ballot(pre) != 0ull) {  // wave-uniform: some lane may reach alpha >= 1/255
             if constexpr (!FULL_ROWS) fetch_rest(r);
             // select form (see blend_backward_kernel): lanes that are not hit run with alpha = G = 0, every update a no-op
-            const float G0 = __builtin_amdgcn_exp2f(p2);
-            const float alpha0 = fminf(0.99f, r.g1.w * G0);
-            const bool hit = pre && !(alpha0 < 1.0f / 255.0f);
+            float G0;
+            const float alpha0 = blend_alpha(r.g1.w, p2, G0);
+            const bool hit = pre && !(alpha0 < ALPHA_MIN);
             const float alpha = hit ? alpha0 : 0.f, G = hit ? G0 : 0.f;
             const float rc = __builtin_amdgcn_rcpf(1.f - alpha);
             const float Tn = T * rc;  // transmittance in front of this Gaussian
@@ -1469,9 +1433,7 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
           // ---- hop 1: (r, w) of the four Gaussians, pixel lanes -> reducer lanes (row = Gaussian, c = lane & 15)
 #pragma unroll
           for (int u = 0; u < 4; u++) *reinterpret_cast<float2 *>(&s_rw[lane * FX_LROW + 2 * u]) = make_float2(accr[u], accw[u]);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          wave_lds_sync();
           float2 rw[4];
 #pragma unroll
           for (int q = 0; q < 4; q++) rw[q] = *reinterpret_cast<const float2 *>(&s_rw[((int)(lane & 15) + 16 * q) * FX_LROW + 2 * row]);
@@ -1534,9 +1496,7 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
                 t3[32] = x3[2];
               }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             if (j0 == 0) base_atomic();
             {  // lane (row, k < 6): column k % 3 of the pair's triple k / 3
               const int which = kcol >= 3 ? 1 : 0, k3 = kcol < 6 ? kcol - 3 * which : 0;
@@ -1550,9 +1510,7 @@ __device__ __forceinline__ void blend_backward_features_body(const BlendBwdArgs 
             __builtin_amdgcn_wave_barrier();  // the next pair's (or the next group's) stores stay behind these reads
           }
           if (NL == 0) {  // no live triple at all: the base sums' second hop alone
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             base_atomic();
             __builtin_amdgcn_wave_barrier();
           }

@@ -3,8 +3,8 @@
 // Once the geometry is frozen (the reference's PBR phase: scene/gaussian_model.py:296-306) the only per-Gaussian gradient anybody
 // consumes is   dL/dcolour_k[c] = sum over pixels of  w_k(pixel) . dL/dimage[c](pixel),   w_k = T_k alpha_k,
 // and w_k is exactly what the FORWARD forms, front to back.  So this kernel is a replay of blend_forward_kernel (blend_fwd.hip): the
-// same quadrant waves, the same 64-entry batches culled and compacted into LDS, the same alpha expression and the same three rules
-// (skip alpha < 1/255, clamp to 0.99, stop at T (1 - alpha) < 1e-4) -- hence the forward's contributors and the forward's weights.
+// same quadrant waves on the same visiting slots, the same 64-entry batches culled and compacted into LDS, and the same contribution
+// rule, which both take from blend_common.h -- hence the forward's contributors and the forward's weights.
 // There is no division of T, no dL/dalpha recursion, no conic or mean moment, and GeomState::grad_rows is never touched.  Lists are
 // walked whole from the slot of their first segment, as the forward walks them (the forward's checkpoints are not read).
 //
@@ -18,7 +18,7 @@
 //     added to the outputs with lane -> (row = lane / 21, column = lane % 21): a Gaussian's live columns are CONTIGUOUS lanes of
 //     one atomic wave-instruction, three Gaussians per instruction (72-byte rows of dL_dextra, 12-byte rows of dL_dcolor).
 // A null gradient image has no plane in LDS, no sums and no atomics: its columns keep the zeros the entry point wrote.
-#include "gsr_common.h"
+#include "blend_common.h"
 
 namespace gsr {
 
@@ -28,22 +28,9 @@ constexpr int CB_COLS = CE_MAX + 3;  // result columns: the extra channels, then
 constexpr int CB_RS = 24;            // floats per result row
 constexpr int CB_WPG = 4;            // the four quadrant waves of a tile share a workgroup (one L1 for the tile's records); no barriers
 
-// bijective XCD-aware remap (as blend_fwd.hip): consecutive work items, which share Gaussians, land on the same XCD / L2
-__device__ __forceinline__ uint32_t cb_xcd_remap(uint32_t bid, uint32_t n) {
-  const uint32_t q = n / 8, r = n % 8, xcd = bid % 8, k = bid / 8;
-  const uint32_t start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return start + k;
-}
-
-__device__ __forceinline__ void cb_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(const BlendColorsBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float s_g_dyn[];  // [wave][3 n_img][64] gradient of the wave's pixels, live images only
-  __shared__ float4 s0_all[CB_WPG * WAVE];  // x, y, qa, qb                                   (as blend_forward_kernel)
+  __shared__ float4 s0_all[CB_WPG * WAVE];  // x, y, qa, qb
   __shared__ float4 s1_all[CB_WPG * WAVE];  // qc, log2(255 opacity) | Gaussian id (bits), opacity
   __shared__ __attribute__((aligned(16))) float s_w_all[CB_WPG * CB_STAGE * CB_WS];
   __shared__ float s_res_all[CB_WPG * CB_STAGE * CB_RS];
@@ -54,11 +41,11 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
   float *s_w = s_w_all + wv * CB_STAGE * CB_WS, *s_res = s_res_all + wv * CB_STAGE * CB_RS;
   uint32_t *s_id = s_id_all + wv * CB_STAGE;
 
-  // workgroup -> tile, exactly as blend_forward_kernel<1, 0>: a list is walked whole from the slot of its first segment
+  // one workgroup per visiting slot: a list is walked whole from the slot of its first segment
   const int omode = tile_order_mode(a.order);
   const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
   uint32_t slot = blockIdx.x;
-  if (!omode) slot = slot < n_slots ? cb_xcd_remap(slot, n_slots) : n_slots;
+  if (!omode) slot = slot < n_slots ? xcd_remap(slot, n_slots) : n_slots;
   const uint32_t entry = tile_of_slot(a.order, omode, slot, n_slots);
   if (entry == ORDER_NO_TILE || order_entry_seg(entry) != 0u) return;  // (workgroup-uniform)
   const uint32_t tile = order_entry_tile(entry), part = wv;
@@ -72,7 +59,7 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
   const int py = ty * TILE + (int)(part >> 1) * 8 + (int)(lane >> 3);
   const float pxf = (float)px, pyf = (float)py;
   const bool inside = px < a.W && py < a.H;
-  float dbias = inside ? -0.02f : 1e30f;  // threshold of the alpha test: -0.02 while the pixel is live, +1e30 once it is done
+  float dbias = inside ? CUT_LIVE : CUT_DONE;
   float T = 1.0f;
   const float rx0 = (float)(tx * TILE + (int)(part & 1u) * 8), rx1 = rx0 + 7.f;
   const float ry0 = (float)(ty * TILE + (int)(part >> 1) * 8), ry1 = ry0 + 7.f;
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
 
   // ---- flush: the staged rows' sums and their atomics (see the header)
   auto flush = [&](int cnt) {
-    cb_wave_sync();  // the staged weights, ids (and, the first time, the gradient planes) are in LDS
+    wave_lds_sync();  // the staged weights, ids (and, the first time, the gradient planes) are in LDS
     const int k = (int)(lane & 15u), j = (int)(lane >> 4);
     float4 w4[4];
 #pragma unroll
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
       acc2 += __shfl_xor(acc2, 32, WAVE);
       if (j < 3) s_res[k * CB_RS + (int)((a.col0 >> (5 * t)) & 31u) + j] = j == 0 ? acc0 : (j == 1 ? acc1 : acc2);
     }
-    cb_wave_sync();
+    wave_lds_sync();
     const int rr = (int)lane / CB_COLS, col = (int)lane % CB_COLS;  // (lane 63: row 3, never used)
     const bool col_live = rr < 3 && ((a.col_mask >> col) & 1u) != 0u;
     for (int r0 = 0; r0 < cnt; r0 += 3) {
@@ -130,10 +117,10 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
         atomicAdd(dst, s_res[row * CB_RS + col]);
       }
     }
-    cb_wave_sync();  // the next staged rows are written behind these reads
+    wave_lds_sync();  // the next staged rows are written behind these reads
   };
 
-  // ---- the forward's walk (blend_fwd.hip): two-stage prefetch of the list, cull + compaction per batch of 64 entries
+  // ---- the forward's walk: two-stage prefetch of the list, cull + compaction per batch of 64 entries
   uint32_t id_a = 0, id_cur = 0;
   float4 p0 = make_float4(0, 0, 0, 0), p1 = p0, p2 = p0;
   if ((int)lane < n) {
@@ -175,7 +162,7 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
       p2 = src[2];
     }
     if (idx + 2 * WAVE < n) id_a = a.point_list[range.x + idx + 2 * WAVE];
-    cb_wave_sync();
+    wave_lds_sync();
 
     // the rows of survivor k + 1 are requested before the arithmetic of survivor k (two register sets used in turn, as the forward)
     struct Row {
@@ -187,16 +174,15 @@ __global__ __launch_bounds__(WAVE * CB_WPG) void blend_colors_backward_kernel(co
       r.g1 = s1[kk];
     };
     auto blend_one = [&](const Row &r) {
-      const float dx = r.g0.x - pxf, dy = r.g0.y - pyf;
-      const float pw = dx * (r.g0.z * dx + r.g0.w * dy) + (r.g1.x * dy) * dy;  // power * log2(e)
-      const bool pre = !(pw > 0.0f) && ((pw + r.g1.y) >= dbias);
+      float pw;
+      const bool pre = cutoff_pre(r.g0, r.g1, pxf, pyf, dbias, pw);
       if (__ballot(pre) != 0ull) {
-        const float alpha = fminf(0.99f, r.g1.w * __builtin_amdgcn_exp2f(pw));
-        const bool hit = pre && !(alpha < 1.0f / 255.0f);
+        const float alpha = blend_alpha(r.g1.w, pw);
+        const bool hit = pre && !(alpha < ALPHA_MIN);
         const float test_T = T * (1.0f - alpha);
-        const bool stop = hit && test_T < 0.0001f;
+        const bool stop = hit && test_T < T_MIN;
         const bool blend = hit && !stop;
-        dbias = stop ? 1e30f : dbias;
+        dbias = stop ? CUT_DONE : dbias;
         const float w = blend ? alpha * T : 0.0f;
         T = blend ? test_T : T;
         if (__ballot(blend) != 0ull) {  // (wave-uniform) somebody blended it: stage the row

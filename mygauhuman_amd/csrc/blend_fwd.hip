@@ -15,7 +15,7 @@
 // Results follow the reference's rules exactly: skip power > 0, alpha = min(0.99, o*exp(power)), skip alpha < 1/255,
 // stop (without blending) when T*(1-alpha) < 1e-4, alpha image = sum of weights, depth image = sum z*w.  Culling is
 // conservative, so it only removes work whose outcome is "skip".
-#include "gsr_common.h"
+#include "blend_common.h"
 #include "tile_sort.h"
 
 #ifndef FWD_FULL_ROWS
@@ -26,13 +26,6 @@
 #endif
 
 namespace gsr {
-
-// bijective XCD-aware remap: consecutive work items (which share Gaussians) land on the same XCD / L2
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t n) {
-  const uint32_t q = n / 8, r = n % 8, xcd = bid % 8, k = bid / 8;
-  const uint32_t start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return start + k;
-}
 
 // CE > 0: fused multi-feature blend -- CE extra colour channels (a.extra[P][CE]) are composited with the same weights in
 // the same pass (the reference rasterises seven times per frame for them, gaussian_renderer/__init__.py:203-272).
@@ -168,7 +161,7 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
     pxf[s] = (float)px;
     pyf[s] = (float)py;
     inside[s] = px < a.W && py < a.H;
-    dbias[s] = inside[s] ? -0.02f : 1e30f;
+    dbias[s] = inside[s] ? CUT_LIVE : CUT_DONE;
     pixid[s] = py * a.W + px;
     T[s] = 1.0f;
     C0[s] = C1[s] = C2[s] = Dp[s] = Wt[s] = 0.f;
@@ -262,9 +255,7 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
       p2 = src[2];
     }
     if (idx + 2 * WAVE < n) id_a = list_at(idx + 2 * WAVE);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // ---- blend the survivors.  Software pipeline: the LDS rows of survivor k + 1 are requested BEFORE the arithmetic of survivor k.
     // A wave's walk is one dependent chain (LDS read -> cut-off test -> branch -> LDS read -> blend), ~500 cycles per survivor when
@@ -296,18 +287,16 @@ __global__ __launch_bounds__((WAVE * fwd_wpg<SLOTS, CE>())) void blend_forward_k
     auto blend_one = [&](Row &r) {
 #pragma unroll
       for (int s = 0; s < SLOTS; s++) {
-        const float dx = r.g0.x - pxf[s], dy = r.g0.y - pyf[s];
-        const float p2 = dx * (r.g0.z * dx + r.g0.w * dy) + (r.g1.x * dy) * dy;  // power * log2(e)
-        // cheap necessary condition for alpha >= 1/255:  log2(255*o) + power*log2(e) >= 0  (0.02 safety margin)
-        const bool pre = !(p2 > 0.0f) && ((p2 + r.g1.y) >= dbias[s]);
+        float pw;
+        const bool pre = cutoff_pre(r.g0, r.g1, pxf[s], pyf[s], dbias[s], pw);
         if (__ballot(pre) != 0ull) {
           if constexpr (!FULL) fetch_rest(r);
-          const float alpha = fminf(0.99f, r.g1.w * __builtin_amdgcn_exp2f(p2));
-          const bool hit = pre && !(alpha < 1.0f / 255.0f);
+          const float alpha = blend_alpha(r.g1.w, pw);
+          const bool hit = pre && !(alpha < ALPHA_MIN);
           const float test_T = T[s] * (1.0f - alpha);
-          const bool stop = hit && test_T < 0.0001f;
+          const bool stop = hit && test_T < T_MIN;
           const bool blend = hit && !stop;
-          dbias[s] = stop ? 1e30f : dbias[s];
+          dbias[s] = stop ? CUT_DONE : dbias[s];
           const float w = blend ? alpha * T[s] : 0.0f;
           C0[s] += r.g2.x * w;
           C1[s] += r.g2.y * w;
@@ -434,7 +423,7 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_features_kernel(const 
   const int py = ty * TILE + (int)(part >> 1) * 8 + (int)(lane >> 3);
   const float pxf = (float)px, pyf = (float)py;
   const bool inside = px < a.W && py < a.H;
-  float dbias = inside ? -0.02f : 1e30f;   // threshold of the alpha test: -0.02 while live, +1e30 once done
+  float dbias = inside ? CUT_LIVE : CUT_DONE;
   const int pixid = py * a.W + px;
   float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f, Wt = 0.f;
   float X[CE];
@@ -502,25 +491,22 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_features_kernel(const 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (__ballot(!(dbias > 0.f)) == 0ull) break;   // every pixel of the wave is saturated (nothing is in flight here)
     const int cnt_next = (j + 1) * HALF < n ? stage(j + 1) : 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int sb = (j & 1) * HALF;
     for (int k = 0; k < cnt; k++) {
       const float4 g0 = s0w[sb + k];
       const float4 g1 = s1w[sb + k];
-      const float dx = g0.x - pxf, dy = g0.y - pyf;
-      const float pw = dx * (g0.z * dx + g0.w * dy) + (g1.x * dy) * dy;  // power * log2(e)
-      const bool pre = !(pw > 0.0f) && ((pw + g1.y) >= dbias);
+      float pw;
+      const bool pre = cutoff_pre(g0, g1, pxf, pyf, dbias, pw);
       if (__ballot(pre) != 0ull) {
         const float4 g2 = s2w[sb + k];
         const uint32_t L = s_lanew[sb + k];
-        const float alpha = fminf(0.99f, g1.w * __builtin_amdgcn_exp2f(pw));
-        const bool hit = pre && !(alpha < 1.0f / 255.0f);
+        const float alpha = blend_alpha(g1.w, pw);
+        const bool hit = pre && !(alpha < ALPHA_MIN);
         const float test_T = T * (1.0f - alpha);
-        const bool stop = hit && test_T < 0.0001f;
+        const bool stop = hit && test_T < T_MIN;
         const bool blend = hit && !stop;
-        dbias = stop ? 1e30f : dbias;
+        dbias = stop ? CUT_DONE : dbias;
         const float w = blend ? alpha * T : 0.0f;
         C0 += g2.x * w;
         C1 += g2.y * w;
@@ -608,18 +594,18 @@ template <int CE>
 __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendFwdArgs a) {
   constexpr int XS = (CE + 3) / 4 * 4;  // floats per survivor row of extra channels (whole 16-byte reads)
   __shared__ float4 s_x_all[CE > 0 ? 4 * WAVE * XS / 4 : 1];
-  __shared__ float4 s0_all[4 * WAVE];  // x, y, qa, qb                        (as blend_forward_kernel)
+  __shared__ float4 s0_all[4 * WAVE];  // x, y, qa, qb
   __shared__ float4 s1_all[4 * WAVE];  // qc, log2(255 opacity) | list position + 1 (bits), opacity
   __shared__ float4 s2_all[4 * WAVE];  // r, g, b, depth
   const uint32_t wv = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
   float4 *s_x = s_x_all + (CE > 0 ? wv * WAVE * XS / 4 : 0);
   float4 *s0 = s0_all + wv * WAVE, *s1 = s1_all + wv * WAVE, *s2 = s2_all + wv * WAVE;
 
-  // workgroup = the four 4x4 blocks of one quadrant of a tile; (slot, quadrant) as in the backward kernels
+  // workgroup = the four 4x4 blocks of one quadrant of a tile
   const int omode = tile_order_mode(a.order);
   const uint32_t n_slots = tile_slots_of(a.order, a.grid_x, a.grid_y, omode);
-  const uint32_t item = omode ? ordered_item4(blockIdx.x, n_slots) : (blockIdx.x < n_slots * 4u ? xcd_remap(blockIdx.x, n_slots * 4u) : n_slots * 4u);
-  const uint32_t entry = tile_of_slot(a.order, omode, item / 4u, n_slots), quad = item % 4u;
+  uint32_t quad;
+  const uint32_t entry = entry_of_quadrant_workgroup(a.order, omode, n_slots, quad);
   if (entry == ORDER_NO_TILE || order_entry_seg(entry) != 0u) return;  // (workgroup-uniform; frames of this variant are binned without segments)
   const uint32_t tile = order_entry_tile(entry);
   const int tx = tile % a.grid_x, ty = tile / a.grid_x;
@@ -640,7 +626,7 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
   const float rx0 = (float)x0, rx1 = (float)(x0 + 3), ry0 = (float)y0, ry1 = (float)(y0 + 3);
   const bool inside = px < a.W && py < a.H;
   const int pixid = py * a.W + px;
-  float dbias = inside ? -0.02f : 1e30f;  // threshold of the alpha test: -0.02 while the pixel is live, +1e30 once it is done
+  float dbias = inside ? CUT_LIVE : CUT_DONE;
   float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f, Wt = 0.f;
   float X[CE > 0 ? CE : 1];
 #pragma unroll
@@ -648,7 +634,7 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
   uint32_t last = 0;
   const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 
-  // list walk exactly as blend_forward_kernel: records of the next batch and list entries of the one after it are in flight
+  // list walk of blend_forward_kernel: records of the next batch and list entries of the one after it are in flight
   uint32_t id_a = 0, id_cur = 0;
   float4 p0 = make_float4(0, 0, 0, 0), p1 = p0, p2 = p0;
   if ((int)lane < n) {
@@ -693,9 +679,7 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
       p2 = src[2];
     }
     if (idx + 2 * WAVE < n) id_a = a.point_list[range.x + idx + 2 * WAVE];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
 
     // ---- blend: four survivors per step (row g of the wave takes survivor j + g); the rows of the NEXT step are requested
     // before this step's arithmetic (two register sets used in turn)
@@ -715,19 +699,19 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
     };
     auto step = [&](const Row &r, int j) {
       const bool valid = j + g < cnt;
-      const float dx = r.g0.x - pxf, dy = r.g0.y - pyf;
-      const float pw = dx * (r.g0.z * dx + r.g0.w * dy) + (r.g1.x * dy) * dy;  // power * log2(e)
-      const bool pre = valid && !(pw > 0.0f) && ((pw + r.g1.y) >= dbias);
+      float pw;
+      const bool cut = cutoff_pre(r.g0, r.g1, pxf, pyf, dbias, pw);
+      const bool pre = valid && cut;
       if (__ballot(pre) != 0ull) {
-        const float alpha = fminf(0.99f, r.g1.w * __builtin_amdgcn_exp2f(pw));
-        const bool hit = pre && !(alpha < 1.0f / 255.0f);
+        const float alpha = blend_alpha(r.g1.w, pw);
+        const bool hit = pre && !(alpha < ALPHA_MIN);
         const float f = hit ? 1.0f - alpha : 1.0f;
         float f0, f1, f2, f3;
         gather_rows(f, f0, f1, f2, f3);
         const float t1 = T * f0, t2 = t1 * f1, t3 = t2 * f2, t4 = t3 * f3;  // the reference's running T after each of the four
         const float tb = g == 0 ? T : (g == 1 ? t1 : (g == 2 ? t2 : t3));  // T in front of this row's survivor
         const float tn = tb * f;                                             // (bit-identical to t1 / t2 / t3 / t4 of this row)
-        const bool blend = hit && !(tn < 0.0001f);
+        const bool blend = hit && !(tn < T_MIN);
         const float w = blend ? alpha * tb : 0.0f;
         C0 += r.g2.x * w;
         C1 += r.g2.y * w;
@@ -743,11 +727,11 @@ __global__ __launch_bounds__(WAVE * 4) void blend_forward_sp_kernel(const BlendF
         }
         last = blend ? __float_as_uint(r.g1.z) : last;
         // the pixel's T after the step: the last product still >= 1e-4 (a stop leaves T in front of the stopping survivor)
-        float Tn = (t4 < 0.0001f) ? t3 : t4;
-        Tn = (t3 < 0.0001f) ? t2 : Tn;
-        Tn = (t2 < 0.0001f) ? t1 : Tn;
-        Tn = (t1 < 0.0001f) ? T : Tn;
-        dbias = (t4 < 0.0001f) ? 1e30f : dbias;
+        float Tn = (t4 < T_MIN) ? t3 : t4;
+        Tn = (t3 < T_MIN) ? t2 : Tn;
+        Tn = (t2 < T_MIN) ? t1 : Tn;
+        Tn = (t1 < T_MIN) ? T : Tn;
+        dbias = (t4 < T_MIN) ? CUT_DONE : dbias;
         T = Tn;
       }
     };
